@@ -21,7 +21,15 @@ the ranks).  Either is one job, bitwise the one-GPU trajectory -> value = that
 job's linearisations / wall time, "strong" scaling.  --multi replicas runs N
 independent copies instead ("weak").
 
-    python bench.py [--gpus N --steps K --warmup W --config C3 --no-cpu-baseline]
+A plain run does only what that figure needs: it loads the graph, warms up,
+times the K steps, writes the last step's results (--dump-outputs DIR) and
+prints the result line.  --full adds everything else the benchmark measures:
+the per-launch kernel tables of one extra profiled step, marginals, the
+closest-keyframe search, scan registration, the Gauss-Newton, converged-regime
+and live re-solve lines, the 1M-pose C5 graph and the CPU baseline; the options
+that size or skip those lines take effect only with it.
+
+    python bench.py [--gpus N --steps K --warmup W --config C3 --dump-outputs DIR --full --no-cpu-baseline]
 """
 from __future__ import annotations
 
@@ -475,6 +483,26 @@ def c5_line(default_params, lanes=3, **common):
     return out
 
 
+DUMP_STATS = ("initial_error", "final_error", "iterations", "linearizations", "inner_iterations", "stop_reason")
+DUMP_MAX_ROWS = 2_000_000   # poses.npy stays under 48 MB; a larger graph is sampled
+
+
+def dump_outputs(path, pg, st):
+    """What the last timed step handed its caller, as float64 .npy files:
+    poses.npy ([N, 3] optimised x, y, theta in insertion order; of a graph of
+    more than DUMP_MAX_ROWS poses a fixed, seeded sample of rows), trace.npy
+    (the per-try record of pgo_get_trace without its wall-clock column) and
+    stats.npy (DUMP_STATS of pgo_stats, in that order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    poses = pg.poses()
+    if len(poses) > DUMP_MAX_ROWS:
+        poses = poses[np.sort(np.random.default_rng(0).choice(len(poses), DUMP_MAX_ROWS, replace=False))]
+    np.save(os.path.join(path, "poses.npy"), poses)
+    np.save(os.path.join(path, "trace.npy"), np.ascontiguousarray(pg.trace()[:, :7]))
+    np.save(os.path.join(path, "stats.npy"), np.array([st[k] for k in DUMP_STATS], dtype=np.float64))
+
+
 def log(msg):
     """Progress on stderr (the JSON line is stdout's only output)."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -543,7 +571,18 @@ def main():
                          "one warm-up + one timed optimize (0: skip)")
     ap.add_argument("--max-outer", type=int, default=0,
                     help="profiling runs only: stop each optimize after this many linearisations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything else the benchmark measures: the profiled step "
+                         "(--profile-every), --marginals, --search, --gicp, --gn, --converged, --live, --c5 and the "
+                         "CPU baseline; without it those options have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results to DIR/poses.npy, trace.npy and "
+                         "stats.npy (float64; the same arguments give the same inputs from run to run)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the result line
+        args.profile_every = args.marginals = args.search = args.gicp = 0
+        args.gn = args.converged = args.live = args.c5 = 0
+        args.no_cpu_baseline = True
 
     from graphslam_amd import datasets
     from graphslam_amd.pose_graph import PoseGraph, default_params
@@ -648,7 +687,7 @@ def main():
                 transport = "host-fallback"
     pg.save_values()                     # upload graph + values once; snapshot the initial values
     # the timed steps run the production configuration (no per-launch
-    # profiling); one more, untimed step with every profile_every-th
+    # profiling); with --full one more, untimed step with every profile_every-th
     # factorisation run eagerly with per-launch events feeds the kernel tables
     common = dict(max_outer=args.max_outer, linear_solver=1 if args.solver == "cholesky" else 0,
                   use_graphs=0 if args.no_graphs else 1, lambda_lanes=args.lanes,
@@ -672,6 +711,8 @@ def main():
     log(f"timed steps done: {1e3 * elapsed / args.steps:.1f} ms per step")
     if spec:   # one job: every rank walked the same linearisations
         lin_total /= world
+    if args.dump_outputs and rank == 0:   # before anything below optimises again
+        dump_outputs(args.dump_outputs, pg, results[-1][1])
     # the timed steps' trajectory, read before the profiled step (which may stop
     # early under --max-outer) and the side lines re-optimize
     tries_lin = tries_per_linearization(pg)
@@ -693,12 +734,14 @@ def main():
     scan = None
     if args.gicp and rank == 0:
         scan = scan_registration_bench(args.gicp)
-    log("marginals / search / scan registration done")
+    if args.full:
+        log("marginals / search / scan registration done")
     one = dict(linear_solver=common["linear_solver"], use_graphs=common["use_graphs"])
     gn = gauss_newton_bench(pg, default_params, **one) if args.gn and rank == 0 and not spec else None
     conv = (converged_regime_bench(pg, g, default_params, lambda_lanes=args.lanes, **one)
             if args.converged and rank == 0 and not spec else None)
-    log("Gauss-Newton and converged-regime lines done")
+    if args.full:
+        log("Gauss-Newton and converged-regime lines done")
     # the GPU plan's ordering of g, taken before live_resolve appends to the handle
     nd_order = pg.debug_ordering() if rank == 0 and not args.no_cpu_baseline and world == 1 else None
     live = None
@@ -747,6 +790,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps,
             # the timed optimize ends at GTSAM's stop -- on C3 lambda's upper bound, not
             # convergence (per_step.stop_reason); ms-to-chi2 convergence proper is the

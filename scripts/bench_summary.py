@@ -1,4 +1,5 @@
-"""Print the headline, the factorisation roofline and the per-family table of a bench.py JSON line."""
+"""Print the headline, the factorisation roofline and the per-family table of a `bench.py --full` JSON line
+(a plain run's line has the headline and the factorisation aggregate, no per-family table)."""
 import json
 import sys
 
