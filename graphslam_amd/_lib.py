@@ -41,6 +41,11 @@ PGO_MULTI_HYBRID = 2
 PGO_TRANSPORT_NONE = 0
 PGO_TRANSPORT_RCCL = 1
 PGO_TRANSPORT_HOST = 2
+PGO_LOSS_NONE = 0
+PGO_LOSS_HUBER = 1
+PGO_LOSS_CAUCHY = 2
+PGO_LOSS_GEMAN_MCCLURE = 3
+LOSSES = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
 TRANSPORTS = {0: "none", 1: "rccl", 2: "host"}
 ABI_VERSION = 6
 STOP_REASONS = {0: "converged", 1: "lambda_upper_bound", 2: "max_iterations", 3: "max_outer", 4: "small_cost_change",
@@ -140,6 +145,10 @@ def lib():
         "pgo_add_prior": (C.c_int, [vp, C.c_uint64, dp, dp]),
         "pgo_add_edge": (C.c_int, [vp, C.c_uint64, C.c_uint64, dp, dp]),
         "pgo_add_edges": (C.c_int, [vp, C.c_size_t, u64p, u64p, dp, dp, C.c_int]),
+        "pgo_add_edge_robust": (C.c_int, [vp, C.c_uint64, C.c_uint64, dp, dp, C.c_int, C.c_double]),
+        "pgo_add_edges_robust": (C.c_int, [vp, C.c_size_t, u64p, u64p, dp, dp, C.c_int, C.POINTER(C.c_int), dp,
+                                           C.c_int]),
+        "pgo_get_edge_weights": (C.c_int, [vp, C.c_size_t, C.c_size_t, dp]),
         "pgo_optimize": (C.c_int, [vp, C.POINTER(PgoParams), C.POINTER(PgoStats)]),
         "pgo_get_pose": (C.c_int, [vp, C.c_uint64, dp]),
         "pgo_get_poses": (C.c_int, [vp, C.c_size_t, u64p, dp]),

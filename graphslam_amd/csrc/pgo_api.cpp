@@ -67,6 +67,9 @@ struct pgo_graph {
   std::vector<uint64_t> ek1, ek2;
   std::vector<double> ez;                   // 3 per between factor
   std::vector<double> eom;                  // 6 per factor: O00 O01 O02 O11 O12 O22
+  std::vector<unsigned char> eloss;         // loss kind per between factor (PGO_LOSS_*)
+  std::vector<double> ek;                   // ... and its parameter k (1 with PGO_LOSS_NONE)
+  size_t n_robust = 0;                      // factors with a loss other than NONE: any -> the robust kernels
   std::vector<uint64_t> pk;
   std::vector<double> pz, pom;
   // ---- device state ----
@@ -289,7 +292,7 @@ void free_device(pgo_graph* g, bool keep_plan = false) {
   g->lane_cap = 8;
   DevGraph& d = g->d;
   void* ptrs[] = {d.eij, d.ez, d.eom, d.prior_ptr, d.prior_vtx, d.pz, d.pom, d.row_ptr, d.slot_edge, d.slot_col, d.V,
-                  d.erow, d.brow, d.s1_ptr, d.s1pos, d.eside, d.Dc, d.W, d.D, d.g, d.pose, d.pose_cand, d.pose_saved, d.x, d.r, d.z, d.p, d.q, d.Minv, d.part, d.scal, d.ctrl};
+                  d.erow, d.brow, d.s1_ptr, d.s1pos, d.eside, d.Dc, d.W, d.eloss, d.ek, d.s1fac, d.D, d.g, d.pose, d.pose_cand, d.pose_saved, d.x, d.r, d.z, d.p, d.q, d.Minv, d.part, d.scal, d.ctrl};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   hipStream_t s = d.stream;
@@ -654,6 +657,23 @@ int upload_structure(pgo_graph* g) {
   RC_TRY(h2d(g, d.s1_ptr, s1_ptr.data(), n + 1));
   RC_TRY(h2d(g, d.s1pos, s1pos.data(), ne));
   RC_TRY(h2d(g, d.Dc, Dc.data(), 6 * (size_t)n));
+  if (g->n_robust > 0) {   // robust losses: kind and k in device order, the side-1 lists' factors
+    std::vector<unsigned char> hl(ne);
+    std::vector<double> hk(ne);
+    std::vector<int> s1fac(ne);
+    for (int e = 0; e < ne; e++) {
+      hl[e] = g->eloss[H.dorder[e]];
+      hk[e] = g->ek[H.dorder[e]];
+      s1fac[s1pos[e]] = e;
+    }
+    RC_TRY(dev_alloc(g, &d.eloss, ce));
+    RC_TRY(dev_alloc(g, &d.ek, ce));
+    RC_TRY(dev_alloc(g, &d.s1fac, ce));
+    RC_TRY(h2d(g, d.eloss, hl.data(), ne));
+    RC_TRY(h2d(g, d.ek, hk.data(), ne));
+    RC_TRY(h2d(g, d.s1fac, s1fac.data(), ne));
+    HIP_TRY(g, hipStreamSynchronize(d.stream));   // (the sources are locals)
+  }
   RC_TRY(dev_alloc(g, &d.eij, ce));
   RC_TRY(dev_alloc(g, &d.ez, ce));
   RC_TRY(dev_alloc(g, &d.eom, 3 * ce));
@@ -768,6 +788,9 @@ int append_structure(pgo_graph* g) {
       (size_t)n > g->cap_n || (size_t)ne > g->cap_ne || (int)H.eij.size() != ne_old ||
       (int)H.erow.size() != n_old + 1 || (int)H.s1pos.size() != ne_old || getenv("PGO_NO_APPEND"))
     return 1;
+  // the first robust factor on an all-Gaussian device graph: the full upload
+  // allocates the loss arrays (and the kernels launched change with it)
+  if ((g->n_robust > 0) != (d.eloss != nullptr)) return 1;
   // the new factors, resolved and in device order
   std::vector<int> nd(ne - ne_old);
   std::vector<int2> nij(ne - ne_old);
@@ -1010,6 +1033,22 @@ int append_structure(pgo_graph* g) {
   RC_TRY(staged_h2d(g, sg, d.erow + x0 + 1, erow.data() + x0 + 1, n - x0));
   RC_TRY(staged_h2d(g, sg, d.s1_ptr + y0 + 1, s1_ptr.data() + y0 + 1, n - y0));
   RC_TRY(staged_h2d(g, sg, d.s1pos, s1pos.data(), ne));
+  std::vector<unsigned char> hl;   // (alive until the stream has drained below: a full staging
+  std::vector<double> hk;          // buffer falls back to copies from these)
+  std::vector<int> s1fac;
+  if (d.eloss) {
+    hl.resize(nij.size());
+    hk.resize(nij.size());
+    for (size_t q = 0; q < nij.size(); q++) {
+      hl[q] = g->eloss[nd[q]];
+      hk[q] = g->ek[nd[q]];
+    }
+    s1fac.resize(ne);
+    for (int e = 0; e < ne; e++) s1fac[s1pos[e]] = e;
+    RC_TRY(staged_h2d(g, sg, d.eloss + ne_old, hl.data(), hl.size()));
+    RC_TRY(staged_h2d(g, sg, d.ek + ne_old, hk.data(), hk.size()));
+    RC_TRY(staged_h2d(g, sg, d.s1fac, s1fac.data(), s1fac.size()));
+  }
   {
     std::vector<int> ys;
     for (const int2& ij : nij)
@@ -1576,6 +1615,8 @@ int run_lanes(pgo_graph* g, const pgo_params& p, int nb, const double* lams, dou
     HIP_TRY(g, pgo::launch_error(v, v.pose_cand, v.scal));
     HIP_TRY(g, hipMemcpyAsync(g->h_lanes + 4 * l, v.scal, 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
   }
+  if (d.eloss)   // the linearised error of this linearisation (launch_error_lin), into lane 0's spare slot
+    HIP_TRY(g, hipMemcpyAsync(g->h_lanes + 3, d.scal + 4, sizeof(double), hipMemcpyDeviceToHost, d.stream));
   HIP_TRY(g, hipMemcpyAsync(g->h_lanes + 4 * 8 + 8, g->chol.d_flag, nb * sizeof(int), hipMemcpyDeviceToHost,
                             d.stream));
   HIP_TRY(g, hipEventRecord(ev[4], d.stream));
@@ -1790,7 +1831,78 @@ int pgo_add_edge(pgo_graph* g, uint64_t k1, uint64_t k2, const double z[3], cons
   g->ek2.push_back(k2);
   g->ez.insert(g->ez.end(), z, z + 3);
   g->eom.insert(g->eom.end(), om, om + 6);
+  g->eloss.push_back(PGO_LOSS_NONE);
+  g->ek.push_back(1.0);
   g->dev_structure = false;
+  return PGO_OK;
+}
+
+static int check_loss(pgo_graph* g, int loss, double k) {
+  if (loss < PGO_LOSS_NONE || loss > PGO_LOSS_GEMAN_MCCLURE) return fail(g, PGO_E_ARG, "unknown robust loss");
+  if (loss != PGO_LOSS_NONE && !(std::isfinite(k) && k > 0.0))
+    return fail(g, PGO_E_ARG, "robust loss parameter k must be finite and positive");
+  if (!std::isfinite(k)) return fail(g, PGO_E_ARG, "robust loss parameter k must be finite");
+  return PGO_OK;
+}
+
+int pgo_add_edge_robust(pgo_graph* g, uint64_t k1, uint64_t k2, const double z[3], const double cov[9], int loss,
+                        double k) {
+  if (!g) return PGO_E_ARG;
+  RC_TRY(check_loss(g, loss, k));
+  RC_TRY(pgo_add_edge(g, k1, k2, z, cov));
+  if (loss != PGO_LOSS_NONE) {
+    g->eloss.back() = (unsigned char)loss;
+    g->ek.back() = k;
+    g->n_robust++;
+  }
+  return PGO_OK;
+}
+
+int pgo_add_edges_robust(pgo_graph* g, size_t n, const uint64_t* k1, const uint64_t* k2, const double* z,
+                         const double* cov, int cov_stride, const int* loss, const double* k, int loss_stride) {
+  if (!g || (n && (!k1 || !k2 || !z || !cov || !loss || !k)) || (cov_stride != 0 && cov_stride != 9) ||
+      (loss_stride != 0 && loss_stride != 1))
+    return PGO_E_ARG;
+  for (size_t i = 0; i < (loss_stride ? n : std::min<size_t>(n, 1)); i++) RC_TRY(check_loss(g, loss[i], k[i]));
+  if (g->ek1.capacity() < g->ek1.size() + n) {
+    const size_t ne = with_room(g->ek1.size() + n);
+    g->ek1.reserve(ne);
+    g->ek2.reserve(ne);
+    g->ez.reserve(3 * ne);
+    g->eom.reserve(6 * ne);
+    g->eloss.reserve(ne);
+    g->ek.reserve(ne);
+  }
+  for (size_t i = 0; i < n; i++)
+    RC_TRY(pgo_add_edge_robust(g, k1[i], k2[i], z + 3 * i, cov + (size_t)cov_stride * i,
+                               loss[(size_t)loss_stride * i], k[(size_t)loss_stride * i]));
+  return PGO_OK;
+}
+
+int pgo_get_edge_weights(pgo_graph* g, size_t first, size_t n, double* out) {
+  if (!g || (n && !out)) return PGO_E_ARG;
+  const size_t ne = g->ek1.size();
+  if (first > ne || n > ne - first) return fail(g, PGO_E_ARG, "edge_weights: range past the last between factor");
+  if (n == 0) return PGO_OK;
+  if (g->n_robust == 0) {   // an all-Gaussian graph: every weight is 1
+    std::fill(out, out + n, 1.0);
+    return PGO_OK;
+  }
+  RC_TRY(ensure_device(g));
+  HIP_TRY(g, hipSetDevice(g->device));
+  const DevGraph& d = g->d;
+  double* dw = nullptr;
+  HIP_TRY(g, hipMalloc((void**)&dw, sizeof(double) * ne));
+  std::vector<double> hw(ne);
+  hipError_t e = pgo::launch_edge_weights(d, dw);
+  if (e == hipSuccess) e = hipMemcpyAsync(hw.data(), dw, sizeof(double) * ne, hipMemcpyDeviceToHost, d.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+  (void)hipFree(dw);
+  HIP_TRY(g, e);
+  for (size_t de = 0; de < ne; de++) {
+    const size_t u = (size_t)g->hs.dorder[de];
+    if (u >= first && u < first + n) out[u - first] = hw[de];
+  }
   return PGO_OK;
 }
 
@@ -1803,6 +1915,8 @@ int pgo_add_edges(pgo_graph* g, size_t n, const uint64_t* k1, const uint64_t* k2
     g->ek2.reserve(ne);
     g->ez.reserve(3 * ne);
     g->eom.reserve(6 * ne);
+    g->eloss.reserve(ne);
+    g->ek.reserve(ne);
   }
   for (size_t i = 0; i < n; i++) RC_TRY(pgo_add_edge(g, k1[i], k2[i], z + 3 * i, cov + (size_t)cov_stride * i));
   return PGO_OK;
@@ -1989,6 +2103,11 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
   }
   if (p.linear_solver == PGO_SOLVER_PCG) RC_TRY(unmix_slot_codes(g));
   d.write_all = p.linear_solver == PGO_SOLVER_PCG ? 1 : 0;
+  // robust losses: GTSAM's guard against a vanishing model decrease compares it
+  // with the linearised error sum 0.5 w r^2, which is no longer the error; it
+  // is computed once per linearisation and read back with the first try
+  const bool robust = d.eloss != nullptr;
+  double lin_err = err;
   // One lambda try (GTSAM tryLambda): solve (H + lam I) delta = -g, retract into
   // pose_cand, error there and the linear model decrease; one read-back.
   // out = {solved, new error, delta'H delta, g'delta}.
@@ -2015,7 +2134,8 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
       HIP_TRY(g, pgo::launch_error(d, d.pose_cand, d.scal));
     }
     HIP_TRY(g, hipEventRecord(ev[4], d.stream));
-    RC_TRY(sync_scalars(g, 3));
+    RC_TRY(sync_scalars(g, robust ? 5 : 3));
+    if (robust) lin_err = g->h_scal[4];
     RC_TRY(finish_solve(g, &st, &ss));
     account_linearize();
     st.ms_solve += ms_between(ev[2], ev[3]);
@@ -2098,6 +2218,7 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
       const double cur_err = new_err;
       RoctxRange range_lin("linearisation");
       HIP_TRY(g, pgo::launch_linearize(d, ev[0], ev[1]));
+      if (robust) HIP_TRY(g, pgo::launch_error_lin(d, d.pose, d.scal + 3));
       HIP_TRY(g, hipEventRecord(g->lin_done, d.stream));
       st.linearizations++;
       first_try = true;
@@ -2147,6 +2268,10 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
             RC_TRY(retried([&] { return run_lanes(g, p, nb, &lam_k[me * L], mine.data(), &st); }));
             st.solves += nb;
             account_linearize();
+            if (robust) lin_err = g->h_lanes[3];
+          } else if (robust) {   // (a rank without a try this round still walks the outcomes)
+            RC_TRY(sync_scalars(g, 5));
+            lin_err = g->h_scal[4];
           }
           st.lambda_rounds++;
           if (exchange) {
@@ -2178,7 +2303,7 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
               if (lin_change >= 0) {
                 new_e = try_e = o[1];
                 const double cost_change = err - new_e;
-                if (lin_change > 2.220446049250313e-16 * err) {
+                if (lin_change > 2.220446049250313e-16 * (robust ? lin_err : err)) {
                   fidelity = cost_change / lin_change;
                   success = fidelity > p.min_model_fidelity;
                 }

@@ -5,7 +5,9 @@
 //                row_ptr int, prior_ptr int, D 6 doubles (upper of H_ii),
 //                g 3, Minv 6, PCG x/r/z/p/q 3 each
 //   per factor : eij int2, ez double4 (x, y, c, s), eom 3 x double2
-//                (O00,O01)(O02,O11)(O12,O22) -- Omega upper triangle.  Factors
+//                (O00,O01)(O02,O11)(O12,O22) -- Omega upper triangle; with a
+//                robust loss anywhere in the graph also eloss (1 byte) and ek
+//                (double), see the robust kernels in pgo_kernels.hip.  Factors
 //                are stored in device order, sorted by (ei, ej), so the side-0
 //                slots of a row read consecutive factors.
 //   per slot   : V 9 doubles, structure of arrays (write_all = 1: PCG and
@@ -69,6 +71,12 @@ struct DevGraph {
   double* scal = nullptr;         // [16] device scalars
   int* ctrl = nullptr;            // [4]: done flag, PCG iterations
   hipStream_t stream = nullptr;
+  // robust losses on between factors (null on an all-Gaussian graph, which then
+  // launches the Gaussian kernels only): kind PGO_LOSS_* and parameter k per
+  // factor in device order, and the inverse of s1pos
+  unsigned char* eloss = nullptr;   // [E] loss kind of each factor
+  double* ek = nullptr;             // [E] its parameter k
+  int* s1fac = nullptr;             // [E] factor at each position of the side-1 lists
 };
 
 // partial-sum buffer slices
@@ -85,6 +93,11 @@ int grid_for(int work);
 
 hipError_t launch_linearize(const DevGraph& d, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 hipError_t launch_error(const DevGraph& d, const double4* pose, double* out_scalar);
+// robust graphs only: out2[0] = sum rho (the error), out2[1] = sum 0.5 w r^2 (the
+// linearised error at `pose`, priors included)
+hipError_t launch_error_lin(const DevGraph& d, const double4* pose, double* out2);
+// robust graphs only: out[e] = w(r) of device factor e at d.pose
+hipError_t launch_edge_weights(const DevGraph& d, double* out);
 hipError_t launch_retract(const DevGraph& d, const double* delta);
 hipError_t launch_pcg_init(const DevGraph& d, double lambda);
 hipError_t launch_pcg_spmv(const DevGraph& d, double lambda, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);

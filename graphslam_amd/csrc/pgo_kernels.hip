@@ -554,6 +554,336 @@ __global__ __launch_bounds__(kThreads) void k_spmv(DevGraph d, double lam, const
   }
 }
 
+// ------------------------------------------------------------ robust losses
+// Between factors with an m-estimator (include/pgo.h PGO_LOSS_*, GTSAM's
+// noiseModel::Robust): with r = sqrt(e'Omega e) the factor's error is rho(r)
+// and its linearisation is the Gaussian one with Omega replaced by w(r) Omega,
+// w = rho'(r) / r at the linearisation point (IRLS).  A graph with any such
+// factor (d.eloss != null) runs the kernels below instead of k_linearize /
+// k_linearize_own / k_linearize_side1 / k_error; the formulas are theirs with
+// Omega scaled first.  Every weight is continuous and in (0, 1].
+__device__ __forceinline__ double robust_weight(int kind, double k, double r2) {
+  switch (kind) {
+    case 1: {   // Huber
+      const double r = sqrt(r2);
+      return r <= k ? 1.0 : k / r;
+    }
+    case 2: return 1.0 / (1.0 + r2 / (k * k));   // Cauchy
+    case 3: {   // Geman-McClure: k^4 / (k^2 + r^2)^2
+      const double t = 1.0 / (1.0 + r2 / (k * k));
+      return t * t;
+    }
+    default: return 1.0;
+  }
+}
+
+__device__ __forceinline__ double robust_rho(int kind, double k, double r2) {
+  switch (kind) {
+    case 1: {
+      const double r = sqrt(r2);
+      return r <= k ? 0.5 * r2 : k * (r - 0.5 * k);
+    }
+    case 2: return 0.5 * (k * k) * log1p(r2 / (k * k));
+    case 3: return 0.5 * r2 / (1.0 + r2 / (k * k));   // (k^2 / 2) r^2 / (k^2 + r^2)
+    default: return 0.5 * r2;
+  }
+}
+
+// Residual of between factor (p1, p2, z) and the terms of J1 (J2 = I), as in
+// k_linearize.
+struct BetweenLin {
+  double e0, e1, e2, hc, hs, dt1, dt2;
+};
+
+__device__ __forceinline__ BetweenLin between_lin(const double4 p1, const double4 p2, const double4 z) {
+  BetweenLin b;
+  double hc = p1.z * p2.z + p1.w * p2.w, hs = -p1.w * p2.z + p1.z * p2.w;
+  rot_normalize(hc, hs);
+  const double dx = p2.x - p1.x, dy = p2.y - p1.y;
+  const double hx = p1.z * dx + p1.w * dy, hy = -p1.w * dx + p1.z * dy;
+  double ec = z.z * hc + z.w * hs, es = -z.w * hc + z.z * hs;
+  rot_normalize(ec, es);
+  const double tx = hx - z.x, ty = hy - z.y;
+  b.e0 = z.z * tx + z.w * ty;
+  b.e1 = -z.w * tx + z.z * ty;
+  b.e2 = atan2(es, ec);
+  b.hc = hc;
+  b.hs = hs;
+  b.dt1 = -p2.w * dx + p2.z * dy;
+  b.dt2 = -p2.z * dx - p2.w * dy;
+  return b;
+}
+
+// w(r) of device factor e at the residual b; r^2 = e'Omega e with the unscaled Omega
+__device__ __forceinline__ double factor_weight(const DevGraph& d, int e, const BetweenLin& b, double o00,
+                                                double o01, double o02, double o11, double o12, double o22,
+                                                double* r2_out = nullptr) {
+  const double u0 = o00 * b.e0 + o01 * b.e1 + o02 * b.e2;
+  const double u1 = o01 * b.e0 + o11 * b.e1 + o12 * b.e2;
+  const double u2 = o02 * b.e0 + o12 * b.e1 + o22 * b.e2;
+  const double r2 = b.e0 * u0 + b.e1 * u1 + b.e2 * u2;
+  if (r2_out) *r2_out = r2;
+  return robust_weight(d.eloss[e], d.ek[e], r2);
+}
+
+// k_linearize with every between factor's Omega scaled by its weight.
+template <int G>
+__global__ __launch_bounds__(kThreads) void k_linearize_robust(DevGraph d) {
+  const int lane = threadIdx.x & (G - 1);
+  const int nsg = gridDim.x * (kThreads / G);
+  for (int row = (blockIdx.x * kThreads + threadIdx.x) / G; row < d.n; row += nsg) {
+    double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0, g0 = 0, g1 = 0, g2 = 0;
+    const int beg = d.row_ptr[row], end = d.row_ptr[row + 1];
+#pragma unroll 1
+    for (int k = beg + lane; k < end; k += G) {
+      const int se = d.slot_edge[k];
+      const bool put = d.write_all || (se & 2);
+      const int2 ij = d.eij[se >> 2];
+      const BetweenLin b = between_lin(d.pose[ij.x], d.pose[ij.y], d.ez[se >> 2]);
+      const double2 oA = d.eom[3 * (se >> 2)], oB = d.eom[3 * (se >> 2) + 1], oC = d.eom[3 * (se >> 2) + 2];
+      const double wt = factor_weight(d, se >> 2, b, oA.x, oA.y, oB.x, oB.y, oC.x, oC.y);
+      const double o00 = wt * oA.x, o01 = wt * oA.y, o02 = wt * oB.x, o11 = wt * oB.y, o12 = wt * oC.x,
+                   o22 = wt * oC.y;
+      const double hc = b.hc, hs = b.hs, dt1 = b.dt1, dt2 = b.dt2;
+      const double m00 = -hc * o00 + hs * o01, m01 = -hs * o00 - hc * o01, m02 = dt1 * o00 + dt2 * o01 - o02;
+      const double m10 = -hc * o01 + hs * o11, m11 = -hs * o01 - hc * o11, m12 = dt1 * o01 + dt2 * o11 - o12;
+      const double m20 = -hc * o02 + hs * o12, m21 = -hs * o02 - hc * o12, m22 = dt1 * o02 + dt2 * o12 - o22;
+      const double w0 = o00 * b.e0 + o01 * b.e1 + o02 * b.e2;
+      const double w1 = o01 * b.e0 + o11 * b.e1 + o12 * b.e2;
+      const double w2 = o02 * b.e0 + o12 * b.e1 + o22 * b.e2;
+      double* v = d.V + k;
+      const size_t S = d.nslots;
+      if ((se & 1) == 0) {  // row ei: H_ij = w J1'Omega, H_ii += w J1'Omega J1, g_i += w J1'Omega e
+        if (put) {
+          v[0] = m00; v[S] = m10; v[2 * S] = m20;
+          v[3 * S] = m01; v[4 * S] = m11; v[5 * S] = m21;
+          v[6 * S] = m02; v[7 * S] = m12; v[8 * S] = m22;
+        }
+        a00 += -hc * m00 + hs * m10;
+        a01 += -hc * m01 + hs * m11;
+        a02 += -hc * m02 + hs * m12;
+        a11 += -hs * m01 - hc * m11;
+        a12 += -hs * m02 - hc * m12;
+        a22 += dt1 * m02 + dt2 * m12 - m22;
+        g0 += -hc * w0 + hs * w1;
+        g1 += -hs * w0 - hc * w1;
+        g2 += dt1 * w0 + dt2 * w1 - w2;
+      } else {              // row ej: H_ji = w Omega J1, H_jj += w Omega, g_j += w Omega e
+        if (put) {
+          v[0] = m00; v[S] = m01; v[2 * S] = m02;
+          v[3 * S] = m10; v[4 * S] = m11; v[5 * S] = m12;
+          v[6 * S] = m20; v[7 * S] = m21; v[8 * S] = m22;
+        }
+        a00 += o00; a01 += o01; a02 += o02; a11 += o11; a12 += o12; a22 += o22;
+        g0 += w0; g1 += w1; g2 += w2;
+      }
+    }
+    if (lane == 0) {  // priors are Gaussian
+      for (int q = d.prior_ptr[row]; q < d.prior_ptr[row + 1]; q++) {
+        const double4 x = d.pose[row], pz = d.pz[q];
+        double c = x.z * pz.z + x.w * pz.w, s = -x.w * pz.z + x.z * pz.w;
+        rot_normalize(c, s);
+        const double dx = pz.x - x.x, dy = pz.y - x.y;
+        const double e0 = -(x.z * dx + x.w * dy), e1 = -(-x.w * dx + x.z * dy), e2 = -atan2(s, c);
+        const double2 oA = d.pom[3 * q], oB = d.pom[3 * q + 1], oC = d.pom[3 * q + 2];
+        const double o00 = oA.x, o01 = oA.y, o02 = oB.x, o11 = oB.y, o12 = oC.x, o22 = oC.y;
+        const double w0 = o00 * e0 + o01 * e1 + o02 * e2;
+        const double w1 = o01 * e0 + o11 * e1 + o12 * e2;
+        const double w2 = o02 * e0 + o12 * e1 + o22 * e2;
+        a00 += o00; a01 += o01; a02 += o02; a11 += o11; a12 += o12; a22 += o22;
+        g0 += w0; g1 += w1; g2 += w2;
+      }
+    }
+    a00 = sg_sum<G>(a00); a01 = sg_sum<G>(a01); a02 = sg_sum<G>(a02);
+    a11 = sg_sum<G>(a11); a12 = sg_sum<G>(a12); a22 = sg_sum<G>(a22);
+    g0 = sg_sum<G>(g0); g1 = sg_sum<G>(g1); g2 = sg_sum<G>(g2);
+    if (lane == 0) {
+      double* D = d.D + 6 * (size_t)row;
+      D[0] = a00; D[1] = a01; D[2] = a02; D[3] = a11; D[4] = a12; D[5] = a22;
+      double* g = d.g + 3 * (size_t)row;
+      g[0] = g0; g[1] = g1; g[2] = g2;
+    }
+  }
+}
+
+// k_linearize_own with weighted Omega.  The side-1 diagonal sum of w Omega
+// depends on the values, so Dc (the precomputed sum of Omega) is not used:
+// the factor's weight travels in W's fourth component to
+// k_linearize_side1_robust, which adds w Omega to D with the gradient terms.
+__global__ __launch_bounds__(kThreads, 4) void k_linearize_own_robust(DevGraph d) {
+  __shared__ double sm[9][kThreads];
+  const int t = threadIdx.x;
+  const int r0 = d.brow[blockIdx.x], r1 = d.brow[blockIdx.x + 1];
+  const int e0 = d.erow[r0], e1 = d.erow[r1];
+  const int row = r0 + t;
+  const bool rowt = row < r1;
+  const int rb = rowt ? d.erow[row] : 0, re = rowt ? d.erow[row + 1] : 0;
+  double a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0, g0 = 0, g1 = 0, g2 = 0;
+  for (int c0 = e0; c0 < e1; c0 += kThreads) {
+    const int e = c0 + t;
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0, s8 = 0;
+    if (e < e1) {
+      const int2 ij = d.eij[e];
+      const BetweenLin b = between_lin(d.pose[ij.x], d.pose[ij.y], d.ez[e]);
+      const double2 oA = d.eom[3 * e], oB = d.eom[3 * e + 1], oC = d.eom[3 * e + 2];
+      const double wt = factor_weight(d, e, b, oA.x, oA.y, oB.x, oB.y, oC.x, oC.y);
+      const double o00 = wt * oA.x, o01 = wt * oA.y, o02 = wt * oB.x, o11 = wt * oB.y, o12 = wt * oC.x,
+                   o22 = wt * oC.y;
+      const double hc = b.hc, hs = b.hs, dt1 = b.dt1, dt2 = b.dt2;
+      const double m00 = -hc * o00 + hs * o01, m01 = -hs * o00 - hc * o01, m02 = dt1 * o00 + dt2 * o01 - o02;
+      const double m10 = -hc * o01 + hs * o11, m11 = -hs * o01 - hc * o11, m12 = dt1 * o01 + dt2 * o11 - o12;
+      const double m20 = -hc * o02 + hs * o12, m21 = -hs * o02 - hc * o12, m22 = dt1 * o02 + dt2 * o12 - o22;
+      const double w0 = o00 * b.e0 + o01 * b.e1 + o02 * b.e2;
+      const double w1 = o01 * b.e0 + o11 * b.e1 + o12 * b.e2;
+      const double w2 = o02 * b.e0 + o12 * b.e1 + o22 * b.e2;
+      double* v = &sm[0][0] + 9 * t;   // this factor's record, staged
+      if (d.eside[e] == 0) {   // owner block H_ij = M'
+        v[0] = m00; v[1] = m10; v[2] = m20;
+        v[3] = m01; v[4] = m11; v[5] = m21;
+        v[6] = m02; v[7] = m12; v[8] = m22;
+      } else {                 // owner block H_ji = M
+        v[0] = m00; v[1] = m01; v[2] = m02;
+        v[3] = m10; v[4] = m11; v[5] = m12;
+        v[6] = m20; v[7] = m21; v[8] = m22;
+      }
+      d.W[d.s1pos[e]] = make_double4(w0, w1, w2, wt);   // w Omega e and w, row ej's side-1 list order
+      s0 = -hc * m00 + hs * m10;
+      s1 = -hc * m01 + hs * m11;
+      s2 = -hc * m02 + hs * m12;
+      s3 = -hs * m01 - hc * m11;
+      s4 = -hs * m02 - hc * m12;
+      s5 = dt1 * m02 + dt2 * m12 - m22;
+      s6 = -hc * w0 + hs * w1;
+      s7 = -hs * w0 - hc * w1;
+      s8 = dt1 * w0 + dt2 * w1 - w2;
+    }
+    __syncthreads();
+    {   // the chunk's records [9 c0, 9 c0 + nv): 16-byte stores from an even element on
+      const double* sv = &sm[0][0];
+      const int nv = 9 * min(kThreads, e1 - c0), head = c0 & 1;
+      double* dst = d.V + 9 * (size_t)c0;
+      if (head && t == 0) dst[0] = sv[0];
+      for (int k = t; 2 * k + 1 < nv - head; k += kThreads)
+        *reinterpret_cast<double2*>(dst + head + 2 * k) = make_double2(sv[head + 2 * k], sv[head + 2 * k + 1]);
+      if (((nv - head) & 1) && t == 0) dst[nv - 1] = sv[nv - 1];
+    }
+    __syncthreads();
+    if (e < e1) {
+      sm[0][t] = s0; sm[1][t] = s1; sm[2][t] = s2; sm[3][t] = s3; sm[4][t] = s4;
+      sm[5][t] = s5; sm[6][t] = s6; sm[7][t] = s7; sm[8][t] = s8;
+    }
+    __syncthreads();
+    if (rowt) {
+      const int kb = rb > c0 ? rb : c0, ke = re < c0 + kThreads ? re : c0 + kThreads;
+      for (int k = kb - c0; k < ke - c0; k++) {
+        a00 += sm[0][k]; a01 += sm[1][k]; a02 += sm[2][k]; a11 += sm[3][k]; a12 += sm[4][k];
+        a22 += sm[5][k]; g0 += sm[6][k]; g1 += sm[7][k]; g2 += sm[8][k];
+      }
+    }
+    __syncthreads();
+  }
+  if (rowt) {
+    for (int q = d.prior_ptr[row]; q < d.prior_ptr[row + 1]; q++) {   // PriorFactor<Pose2> (Gaussian)
+      const double4 p1 = d.pose[row], pz = d.pz[q];
+      double c = p1.z * pz.z + p1.w * pz.w, s = -p1.w * pz.z + p1.z * pz.w;
+      rot_normalize(c, s);
+      const double dx = pz.x - p1.x, dy = pz.y - p1.y;
+      const double e0 = -(p1.z * dx + p1.w * dy), e1 = -(-p1.w * dx + p1.z * dy), e2 = -atan2(s, c);
+      const double2 oA = d.pom[3 * q], oB = d.pom[3 * q + 1], oC = d.pom[3 * q + 2];
+      const double o00 = oA.x, o01 = oA.y, o02 = oB.x, o11 = oB.y, o12 = oC.x, o22 = oC.y;
+      const double w0 = o00 * e0 + o01 * e1 + o02 * e2;
+      const double w1 = o01 * e0 + o11 * e1 + o12 * e2;
+      const double w2 = o02 * e0 + o12 * e1 + o22 * e2;
+      a00 += o00; a01 += o01; a02 += o02; a11 += o11; a12 += o12; a22 += o22;
+      g0 += w0; g1 += w1; g2 += w2;
+    }
+    double* D = d.D + 6 * (size_t)row;
+    D[0] = a00; D[1] = a01; D[2] = a02; D[3] = a11; D[4] = a12; D[5] = a22;
+    double* g = d.g + 3 * (size_t)row;
+    g[0] = g0; g[1] = g1; g[2] = g2;
+  }
+}
+
+// Row j's side-1 terms after k_linearize_own_robust: g_j += sum of w Omega e
+// and H_jj += sum of w Omega over the factors with ej = j, in device factor
+// order (W's list order) with the same fixed-order sub-group sum; s1fac gives
+// the factor whose Omega a list position reads.
+template <int G>
+__global__ __launch_bounds__(kThreads) void k_linearize_side1_robust(DevGraph d) {
+  const int lane = threadIdx.x & (G - 1);
+  const int nsg = gridDim.x * (kThreads / G);
+  for (int row = (blockIdx.x * kThreads + threadIdx.x) / G; row < d.n; row += nsg) {
+    double s0 = 0, s1 = 0, s2 = 0, a00 = 0, a01 = 0, a02 = 0, a11 = 0, a12 = 0, a22 = 0;
+    for (int t = d.s1_ptr[row] + lane; t < d.s1_ptr[row + 1]; t += G) {
+      const double4 w = d.W[t];
+      const int e = d.s1fac[t];
+      const double2 oA = d.eom[3 * e], oB = d.eom[3 * e + 1], oC = d.eom[3 * e + 2];
+      s0 += w.x; s1 += w.y; s2 += w.z;
+      a00 += w.w * oA.x; a01 += w.w * oA.y; a02 += w.w * oB.x;
+      a11 += w.w * oB.y; a12 += w.w * oC.x; a22 += w.w * oC.y;
+    }
+    s0 = sg_sum<G>(s0); s1 = sg_sum<G>(s1); s2 = sg_sum<G>(s2);
+    a00 = sg_sum<G>(a00); a01 = sg_sum<G>(a01); a02 = sg_sum<G>(a02);
+    a11 = sg_sum<G>(a11); a12 = sg_sum<G>(a12); a22 = sg_sum<G>(a22);
+    if (lane == 0) {
+      double* g = d.g + 3 * (size_t)row;
+      g[0] += s0; g[1] += s1; g[2] += s2;
+      double* D = d.D + 6 * (size_t)row;
+      D[0] += a00; D[1] += a01; D[2] += a02; D[3] += a11; D[4] += a12; D[5] += a22;
+    }
+  }
+}
+
+// Robust graph error: rho(r) per between factor, 0.5 e'Omega e per prior
+// (slice A), and the linearised error sum of 0.5 w r^2 at the same values
+// (slice A + 1: what LM's guard against a vanishing model decrease compares).
+__global__ __launch_bounds__(kThreads) void k_error_robust(DevGraph d, const double4* __restrict__ pose) {
+  __shared__ double lds[kThreads / 64];
+  double acc = 0.0, lin = 0.0;
+  const int total = d.ne + d.np;
+  for (int t = blockIdx.x * kThreads + threadIdx.x; t < total; t += gridDim.x * kThreads) {
+    if (t < d.ne) {
+      const int2 ij = d.eij[t];
+      const BetweenLin b = between_lin(pose[ij.x], pose[ij.y], d.ez[t]);
+      const double2 oA = d.eom[3 * t], oB = d.eom[3 * t + 1], oC = d.eom[3 * t + 2];
+      double r2;
+      const double wt = factor_weight(d, t, b, oA.x, oA.y, oB.x, oB.y, oC.x, oC.y, &r2);
+      acc += robust_rho(d.eloss[t], d.ek[t], r2);
+      lin += 0.5 * wt * r2;
+    } else {
+      const int q = t - d.ne;
+      const double4 x = pose[d.prior_vtx[q]], pz = d.pz[q];
+      double c = x.z * pz.z + x.w * pz.w, s = -x.w * pz.z + x.z * pz.w;
+      rot_normalize(c, s);
+      const double dx = pz.x - x.x, dy = pz.y - x.y;
+      const double e0 = -(x.z * dx + x.w * dy), e1 = -(-x.w * dx + x.z * dy), e2 = -atan2(s, c);
+      const double2 oA = d.pom[3 * q], oB = d.pom[3 * q + 1], oC = d.pom[3 * q + 2];
+      const double w0 = oA.x * e0 + oA.y * e1 + oB.x * e2;
+      const double w1 = oA.y * e0 + oB.y * e1 + oC.x * e2;
+      const double w2 = oB.x * e0 + oC.x * e1 + oC.y * e2;
+      const double h = 0.5 * (e0 * w0 + e1 * w1 + e2 * w2);
+      acc += h;
+      lin += h;
+    }
+  }
+  acc = block_sum(acc, lds);
+  lin = block_sum(lin, lds);
+  if (threadIdx.x == 0) {
+    d.part[kPartA * kMaxBlocks + blockIdx.x] = acc;
+    d.part[(kPartA + 1) * kMaxBlocks + blockIdx.x] = lin;
+  }
+}
+
+// w(r) of every between factor at d.pose, device factor order (pgo_get_edge_weights)
+__global__ __launch_bounds__(kThreads) void k_edge_weights(DevGraph d, double* __restrict__ out) {
+  for (int t = blockIdx.x * kThreads + threadIdx.x; t < d.ne; t += gridDim.x * kThreads) {
+    const int2 ij = d.eij[t];
+    const BetweenLin b = between_lin(d.pose[ij.x], d.pose[ij.y], d.ez[t]);
+    const double2 oA = d.eom[3 * t], oB = d.eom[3 * t + 1], oC = d.eom[3 * t + 2];
+    out[t] = factor_weight(d, t, b, oA.x, oA.y, oB.x, oB.y, oC.x, oC.y);
+  }
+}
+
 // ------------------------------------------------------------ launchers
 int grid_for(int work) {
   int b = (work + kThreads - 1) / kThreads;
@@ -581,6 +911,16 @@ hipError_t launch_linearize(const DevGraph& d, hipEvent_t start, hipEvent_t stop
   const dim3 block(kThreads);
   if (!d.write_all && d.eside) {   // Cholesky mode: owner blocks in factor order
     const dim3 grid1((unsigned)(((long long)d.n * d.G1 + kThreads - 1) / kThreads));
+    if (d.eloss) {   // robust losses: weighted Omega, side-1 diagonal summed on the device
+      hipExtLaunchKernelGGL(k_linearize_own_robust, dim3(d.nlb), block, 0, d.stream, start, nullptr, 0, d);
+      switch (d.G1) {
+        case 4: hipExtLaunchKernelGGL(k_linearize_side1_robust<4>, grid1, block, 0, d.stream, nullptr, stop, 0, d); break;
+        case 8: hipExtLaunchKernelGGL(k_linearize_side1_robust<8>, grid1, block, 0, d.stream, nullptr, stop, 0, d); break;
+        case 16: hipExtLaunchKernelGGL(k_linearize_side1_robust<16>, grid1, block, 0, d.stream, nullptr, stop, 0, d); break;
+        default: hipExtLaunchKernelGGL(k_linearize_side1_robust<32>, grid1, block, 0, d.stream, nullptr, stop, 0, d); break;
+      }
+      return hipGetLastError();
+    }
     hipExtLaunchKernelGGL(k_linearize_own, dim3(d.nlb), block, 0, d.stream, start, nullptr, 0, d);
     switch (d.G1) {
       case 4: hipExtLaunchKernelGGL(k_linearize_side1<4>, grid1, block, 0, d.stream, nullptr, stop, 0, d); break;
@@ -591,6 +931,15 @@ hipError_t launch_linearize(const DevGraph& d, hipEvent_t start, hipEvent_t stop
     return hipGetLastError();
   }
   const dim3 grid((unsigned)(((long long)d.n * d.G + kThreads - 1) / kThreads));   // one sub-group per row
+  if (d.eloss) {
+    switch (d.G) {
+      case 4: hipExtLaunchKernelGGL(k_linearize_robust<4>, grid, block, 0, d.stream, start, stop, 0, d); break;
+      case 8: hipExtLaunchKernelGGL(k_linearize_robust<8>, grid, block, 0, d.stream, start, stop, 0, d); break;
+      case 16: hipExtLaunchKernelGGL(k_linearize_robust<16>, grid, block, 0, d.stream, start, stop, 0, d); break;
+      default: hipExtLaunchKernelGGL(k_linearize_robust<32>, grid, block, 0, d.stream, start, stop, 0, d); break;
+    }
+    return hipGetLastError();
+  }
   switch (d.G) {
     case 4: hipExtLaunchKernelGGL(k_linearize<4>, grid, block, 0, d.stream, start, stop, 0, d); break;
     case 8: hipExtLaunchKernelGGL(k_linearize<8>, grid, block, 0, d.stream, start, stop, 0, d); break;
@@ -602,8 +951,24 @@ hipError_t launch_linearize(const DevGraph& d, hipEvent_t start, hipEvent_t stop
 
 hipError_t launch_error(const DevGraph& d, const double4* pose, double* out_scalar) {
   const int nb = grid_for(d.ne + d.np);
-  k_error<<<nb, kThreads, 0, d.stream>>>(d, pose);
+  if (d.eloss) k_error_robust<<<nb, kThreads, 0, d.stream>>>(d, pose);
+  else k_error<<<nb, kThreads, 0, d.stream>>>(d, pose);
   k_reduce<<<1, kThreads, 0, d.stream>>>(d.part, kPartA, 1, nb, out_scalar);
+  return hipGetLastError();
+}
+
+hipError_t launch_error_lin(const DevGraph& d, const double4* pose, double* out2) {
+  if (!d.eloss) return hipErrorInvalidValue;
+  const int nb = grid_for(d.ne + d.np);
+  k_error_robust<<<nb, kThreads, 0, d.stream>>>(d, pose);
+  k_reduce<<<1, kThreads, 0, d.stream>>>(d.part, kPartA, 2, nb, out2);
+  return hipGetLastError();
+}
+
+hipError_t launch_edge_weights(const DevGraph& d, double* out) {
+  if (!d.eloss) return hipErrorInvalidValue;
+  if (d.ne == 0) return hipSuccess;
+  k_edge_weights<<<grid_for(d.ne), kThreads, 0, d.stream>>>(d, out);
   return hipGetLastError();
 }
 

@@ -79,6 +79,10 @@ class PoseGraph:
     prior_pose: np.ndarray      # f64 [P,3]
     prior_cov: np.ndarray       # f64 [P,9]
     meta: dict = field(default_factory=dict)
+    # robust loss per between factor (include/pgo.h PGO_LOSS_*): None = all
+    # Gaussian; a scalar or an int [E] array, with edge_loss_k the parameter k
+    edge_loss: np.ndarray | int | None = None
+    edge_loss_k: np.ndarray | float | None = None
 
     @property
     def num_poses(self) -> int:
@@ -292,6 +296,30 @@ def make(name: str) -> PoseGraph:
     if name not in CONFIGS:
         raise KeyError(f"unknown config {name!r}; have {sorted(CONFIGS) + ['C1-nn']}")
     return manhattan(name=name, **CONFIGS[name])
+
+
+def loop_closure_indices(g):
+    """Indices of the loop-closure factors of a generated graph (its last
+    ``meta['loop_closures']`` between factors)."""
+    m = int(g.meta.get("loop_closures", 0))
+    return np.arange(g.num_edges - m, g.num_edges, dtype=np.int64)
+
+
+def corrupt_loop_closures(g, fraction, seed):
+    """Replace the measurement of ``fraction`` of the loop closures by a random
+    pose (a wrong scan match: x, y uniform over the walk's extent, theta
+    uniform), in place; covariances stay.  Returns the sorted factor indices it
+    replaced.  All randomness from ``numpy.random.default_rng(seed)``."""
+    rng = np.random.default_rng(seed)
+    lc = loop_closure_indices(g)
+    m = int(round(fraction * len(lc)))
+    bad = np.sort(rng.choice(lc, size=m, replace=False)) if m else np.empty(0, np.int64)
+    lo, hi = g.ground_truth[:, :2].min(), g.ground_truth[:, :2].max()
+    g.edge_z = g.edge_z.copy()
+    g.edge_z[bad, 0] = rng.uniform(lo, hi, size=m)
+    g.edge_z[bad, 1] = rng.uniform(lo, hi, size=m)
+    g.edge_z[bad, 2] = rng.uniform(-np.pi, np.pi, size=m)
+    return bad
 
 
 def noise_free(gt, pairs, prior_index=0, name="kat"):

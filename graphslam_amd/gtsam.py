@@ -72,13 +72,68 @@ class _Diagonal:
         return _Gaussian(np.diag(np.asarray(v, dtype=np.float64)))
 
 
+class _MEstimatorBase:
+    """gtsam::noiseModel::mEstimator::Base: a loss kind (PGO_LOSS_*) and its k."""
+
+    loss = 0
+
+    def __init__(self, k):
+        k = float(k)
+        if not (math.isfinite(k) and k > 0.0):
+            raise ValueError("mEstimator parameter k must be finite and positive")
+        self.k = k
+
+    @classmethod
+    def Create(cls, k):
+        return cls(k)
+
+
+class _Huber(_MEstimatorBase):
+    loss = 1
+
+
+class _Cauchy(_MEstimatorBase):
+    loss = 2
+
+
+class _GemanMcClure(_MEstimatorBase):
+    loss = 3
+
+
+class _mEstimator:
+    Huber = _Huber
+    Cauchy = _Cauchy
+    GemanMcClure = _GemanMcClure
+
+
+class _Robust:
+    """gtsam::noiseModel::Robust: an mEstimator over a Gaussian model."""
+
+    def __init__(self, estimator, gaussian):
+        if not isinstance(estimator, _MEstimatorBase):
+            raise TypeError("Robust.Create needs an mEstimator (Huber / Cauchy / GemanMcClure)")
+        if not isinstance(gaussian, _Gaussian):
+            raise TypeError("Robust.Create needs a Gaussian noise model")
+        self.robust, self.noise = estimator, gaussian
+        self.covariance = gaussian.covariance
+
+    @staticmethod
+    def Create(estimator, gaussian):
+        return _Robust(estimator, gaussian)
+
+
 class noiseModel:  # noqa: N801 -- mirrors gtsam::noiseModel
     Gaussian = _Gaussian
     Diagonal = _Diagonal
+    mEstimator = _mEstimator
+    Robust = _Robust
 
 
 class PriorFactorPose2:
     def __init__(self, key, prior: Pose2, noise: _Gaussian):
+        if isinstance(noise, _Robust):
+            raise TypeError("PriorFactorPose2 takes a Gaussian noise model: robust losses are supported on "
+                            "BetweenFactorPose2 only")
         self.key, self.prior, self.noise = int(key), prior, noise
 
     def keys(self):
@@ -111,7 +166,7 @@ class NonlinearFactorGraph:
         return len(self.factors)
 
     def error(self, values: "Values") -> float:
-        """0.5 * sum e' Omega e, computed on the device."""
+        """0.5 * sum e' Omega e (rho(r) for a factor with a robust model), computed on the device."""
         with _build(self, values) as pg:
             return pg.error()
 
@@ -175,7 +230,9 @@ def _build(graph: NonlinearFactorGraph, values: Values, device=0):
         if isinstance(f, PriorFactorPose2):
             pg.add_prior(f.key, [f.prior.x(), f.prior.y(), f.prior._t], f.noise.covariance)
         else:
-            pg.add_edge(f.key1, f.key2, [f.measured.x(), f.measured.y(), f.measured._t], f.noise.covariance)
+            est = f.noise.robust if isinstance(f.noise, _Robust) else None
+            pg.add_edge(f.key1, f.key2, [f.measured.x(), f.measured.y(), f.measured._t], f.noise.covariance,
+                        loss=est.loss if est else None, k=est.k if est else None)
     return _Handle(pg)
 
 

@@ -50,6 +50,14 @@ _EXC = {
 KEYFRAMES_TO_SKIP_IN_LOOP_CLOSING = 10   # graph.cpp:15
 
 
+def _loss_code(loss):
+    if isinstance(loss, str):
+        if loss.lower() not in L.LOSSES:
+            raise ValueError(f"unknown robust loss {loss!r}; have {sorted(L.LOSSES)}")
+        return L.LOSSES[loss.lower()]
+    return int(loss)
+
+
 def default_params(**kw) -> L.PgoParams:
     p = L.PgoParams()
     L.lib().pgo_default_params(C.byref(p))
@@ -72,6 +80,7 @@ class PoseGraph:
         if not self._h:
             raise MemoryError("pgo_create failed")
         self.last_stats = None
+        self._priors = 0
 
     # ------------------------------------------------------------------ utils
     def _check(self, rc):
@@ -110,13 +119,22 @@ class PoseGraph:
         pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(3)
         cov = np.ascontiguousarray(cov, dtype=np.float64).reshape(9)
         self._check(self._L.pgo_add_prior(self._h, int(key), L.dptr(pose), L.dptr(cov)))
+        self._priors += 1
 
-    def add_edge(self, k1, k2, z, cov):
+    def add_edge(self, k1, k2, z, cov, loss=None, k=None):
+        """One between factor; ``loss`` (PGO_LOSS_* or its name in _lib.LOSSES)
+        with parameter ``k`` makes it robust (pgo_add_edge_robust)."""
         z = np.ascontiguousarray(z, dtype=np.float64).reshape(3)
         cov = np.ascontiguousarray(cov, dtype=np.float64).reshape(9)
-        self._check(self._L.pgo_add_edge(self._h, int(k1), int(k2), L.dptr(z), L.dptr(cov)))
+        if loss is None:
+            self._check(self._L.pgo_add_edge(self._h, int(k1), int(k2), L.dptr(z), L.dptr(cov)))
+            return
+        self._check(self._L.pgo_add_edge_robust(self._h, int(k1), int(k2), L.dptr(z), L.dptr(cov),
+                                                _loss_code(loss), 1.0 if k is None else float(k)))
 
-    def add_edges(self, k1, k2, z, cov):
+    def add_edges(self, k1, k2, z, cov, loss=None, k=None):
+        """Bulk between factors; ``loss`` / ``k``: None (Gaussian), scalars
+        (shared by all), or one per edge (pgo_add_edges_robust)."""
         k1 = np.ascontiguousarray(k1, dtype=np.uint64)
         k2 = np.ascontiguousarray(k2, dtype=np.uint64)
         z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, 3)
@@ -124,8 +142,32 @@ class PoseGraph:
         stride = 0 if cov.size == 9 else 9
         if stride and cov.reshape(-1, 9).shape[0] != len(k1):
             raise ValueError("cov must be one [9] or [E,9]")
-        self._check(self._L.pgo_add_edges(self._h, len(k1), L.u64ptr(k1), L.u64ptr(k2), L.dptr(z),
-                                          L.dptr(cov), stride))
+        if loss is None:
+            self._check(self._L.pgo_add_edges(self._h, len(k1), L.u64ptr(k1), L.u64ptr(k2), L.dptr(z),
+                                              L.dptr(cov), stride))
+            return
+        per_edge = np.ndim(loss) > 0 or np.ndim(k) > 0
+        m = len(k1) if per_edge else 1
+        if np.ndim(loss) > 0:
+            codes = np.array([_loss_code(v) for v in loss], dtype=np.int32)
+        else:
+            codes = np.full(m, _loss_code(loss), dtype=np.int32)
+        ks = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if k is None else k, dtype=np.float64), (m,)))
+        if len(codes) != m:
+            raise ValueError("loss must be a scalar or one per edge")
+        self._check(self._L.pgo_add_edges_robust(self._h, len(k1), L.u64ptr(k1), L.u64ptr(k2), L.dptr(z),
+                                                 L.dptr(cov), stride, codes.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 L.dptr(ks), 1 if per_edge else 0))
+
+    def edge_weights(self, first=0, n=None):
+        """w(r) of the between factors [first, first + n) in insertion order at
+        the current values (1.0 for Gaussian factors): low weights mark the loop
+        closures the robust loss has rejected."""
+        if n is None:
+            n = self.num_factors - self._priors - int(first)
+        out = np.zeros(int(n))
+        self._check(self._L.pgo_get_edge_weights(self._h, int(first), int(n), L.dptr(out)))
+        return out
 
     @classmethod
     def from_dataset(cls, g, device=0, ordering=L.PGO_ORDERING_ND):
@@ -134,7 +176,8 @@ class PoseGraph:
         pg.add_vertices(g.keys, g.initial)
         for k, p, c in zip(g.prior_keys, g.prior_pose, g.prior_cov):
             pg.add_prior(int(k), p, c)
-        pg.add_edges(g.edge_k1, g.edge_k2, g.edge_z, g.edge_cov)
+        pg.add_edges(g.edge_k1, g.edge_k2, g.edge_z, g.edge_cov, loss=getattr(g, "edge_loss", None),
+                     k=getattr(g, "edge_loss_k", None))
         return pg
 
     # -------------------------------------------------------------- optimise

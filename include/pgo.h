@@ -232,6 +232,46 @@ int pgo_add_edge(pgo_graph *g, uint64_t k1, uint64_t k2, const double z[3], cons
 int pgo_add_edges(pgo_graph *g, size_t n, const uint64_t *k1, const uint64_t *k2,
                   const double *z, const double *cov, int cov_stride);
 
+/* ---- robust losses on between factors --------------------------------------
+   gtsam::noiseModel::Robust::Create(mEstimator, Gaussian::Covariance(cov)) on a
+   BetweenFactor<Pose2> (GTSAM >= 4.1 mEstimator definitions).  With the
+   whitened residual norm r = sqrt(e^T Omega e) and the parameter k > 0:
+
+     loss                     rho(r)                          w(r) = rho'(r) / r
+     PGO_LOSS_NONE            r^2 / 2                         1
+     PGO_LOSS_HUBER           r^2 / 2            if r <= k    1           if r <= k
+                              k (r - k / 2)      otherwise    k / r       otherwise
+     PGO_LOSS_CAUCHY          (k^2 / 2) log1p(r^2 / k^2)      1 / (1 + r^2 / k^2)
+     PGO_LOSS_GEMAN_MCCLURE   (k^2 / 2) r^2 / (k^2 + r^2)     k^4 / (k^2 + r^2)^2
+
+   The graph error (pgo_error, pgo_stats.initial_error / final_error, the
+   trace's candidate error, LM's cost change) is the sum of rho(r) over the
+   between factors plus the priors' e^T Omega e / 2.  The linearisation is
+   iteratively reweighted least squares (Robust::WhitenSystem): the factor
+   enters H and g with Omega replaced by w(r) Omega, r at the linearisation
+   point; the model decrease is -(g'd + d'H d / 2) on that H and g, and LM's
+   guard against a vanishing model decrease compares it with the linearised
+   error sum of w r^2 / 2.  Marginal covariances and the diagnostics below use
+   the weighted H.  Every weight is continuous and in (0, 1]; priors take no
+   loss.  pgo_add_edge(s) is PGO_LOSS_NONE, and a graph whose factors are all
+   PGO_LOSS_NONE computes what it did before, bit for bit. */
+#define PGO_LOSS_NONE 0
+#define PGO_LOSS_HUBER 1
+#define PGO_LOSS_CAUCHY 2
+#define PGO_LOSS_GEMAN_MCCLURE 3
+/* pgo_add_edge with a loss; an unknown loss, a non-finite k, or k <= 0 with a
+   loss other than PGO_LOSS_NONE -> PGO_E_ARG */
+int pgo_add_edge_robust(pgo_graph *g, uint64_t k1, uint64_t k2, const double z[3], const double cov[9],
+                        int loss, double k);
+/* bulk form; loss_stride 0 = one shared (loss[0], k[0]), 1 = one per edge */
+int pgo_add_edges_robust(pgo_graph *g, size_t n, const uint64_t *k1, const uint64_t *k2,
+                         const double *z, const double *cov, int cov_stride,
+                         const int *loss, const double *k, int loss_stride);
+/* w(r) of the between factors [first, first + n) in insertion order at the
+   current values (device; 1.0 for PGO_LOSS_NONE): a caller rejects the loop
+   closures whose weight ends low */
+int pgo_get_edge_weights(pgo_graph *g, size_t first, size_t n, double *out);
+
 /* ---- optimisation (graph.cpp:119, write-back :122-130) ------------------- */
 /* Runs the optimiser from the handle's current values and replaces them with
  * the result (the reference's `initial = poses_opti`).  NULL params: defaults. */
@@ -267,7 +307,8 @@ int pgo_save_values(pgo_graph *g);
 int pgo_restore_values(pgo_graph *g);
 size_t pgo_num_factors(const pgo_graph *g);   /* graph.nrFactors() */
 size_t pgo_num_vertices(const pgo_graph *g);  /* initial.size()    */
-/* graph.error(values) = 0.5 sum e^T Omega e at the current values (device). */
+/* graph.error(values) = 0.5 sum e^T Omega e at the current values (device);
+ * rho(r) for a between factor with a robust loss (see above). */
 int pgo_error(pgo_graph *g, double *err);
 
 /* ---- marginals ------------------------------------------

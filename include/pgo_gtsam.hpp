@@ -67,6 +67,30 @@ struct Gaussian {
   using shared_ptr = const Gaussian*;  // value semantics suffice here
   static Gaussian Covariance(const Matrix3& q) { return Gaussian{q}; }  // graph.cpp:45,83,103
 };
+// gtsam::noiseModel::mEstimator::{Huber, Cauchy, GemanMcClure}::Create(k): a
+// loss kind (PGO_LOSS_*) and its parameter
+namespace mEstimator {
+struct Base {
+  int loss;
+  double k;
+};
+struct Huber {
+  static Base Create(double k) { return Base{PGO_LOSS_HUBER, k}; }
+};
+struct Cauchy {
+  static Base Create(double k) { return Base{PGO_LOSS_CAUCHY, k}; }
+};
+struct GemanMcClure {
+  static Base Create(double k) { return Base{PGO_LOSS_GEMAN_MCCLURE, k}; }
+};
+}  // namespace mEstimator
+// gtsam::noiseModel::Robust::Create(estimator, gaussian): accepted by
+// BetweenFactor<Pose2> only (a PriorFactor takes a Gaussian model)
+struct Robust {
+  mEstimator::Base robust;
+  Gaussian noise;
+  static Robust Create(const mEstimator::Base& e, const Gaussian& n) { return Robust{e, n}; }
+};
 }  // namespace noiseModel
 
 template <class T>
@@ -82,7 +106,11 @@ struct BetweenFactor {  // gtsam::BetweenFactor<Pose2> (graph.cpp:87-92,106-111)
   Key key1, key2;
   T measured;
   noiseModel::Gaussian noise;
+  int loss = PGO_LOSS_NONE;   // robust model: the mEstimator's kind and parameter
+  double k = 1.0;
   BetweenFactor(Key a, Key b, const T& z, const noiseModel::Gaussian& n) : key1(a), key2(b), measured(z), noise(n) {}
+  BetweenFactor(Key a, Key b, const T& z, const noiseModel::Robust& n)
+      : key1(a), key2(b), measured(z), noise(n.noise), loss(n.robust.loss), k(n.robust.k) {}
 };
 
 class Values {  // gtsam::Values restricted to Pose2
@@ -173,7 +201,7 @@ class LevenbergMarquardtOptimizer {
     }
     for (const auto& f : graph_.betweens()) {
       const double z[3] = {f.measured.x(), f.measured.y(), f.measured.raw_theta()};
-      throw_status(pgo_add_edge(g_, f.key1, f.key2, z, f.noise.cov.m), g_);
+      throw_status(pgo_add_edge_robust(g_, f.key1, f.key2, z, f.noise.cov.m, f.loss, f.k), g_);
     }
     loaded_ = true;
   }
@@ -206,7 +234,7 @@ class Marginals {
     }
     for (const auto& f : graph.betweens()) {
       const double z[3] = {f.measured.x(), f.measured.y(), f.measured.raw_theta()};
-      throw_status(pgo_add_edge(g_, f.key1, f.key2, z, f.noise.cov.m), g_);
+      throw_status(pgo_add_edge_robust(g_, f.key1, f.key2, z, f.noise.cov.m, f.loss, f.k), g_);
     }
   }
   ~Marginals() { pgo_destroy(g_); }
