@@ -34,6 +34,11 @@ constexpr int kInlineTiles = 512;
 constexpr int kLookaheadM = 512;   // fronts this tall skip the next step's column block in their plain tiles
                                    // (2048 until round 4: 512 measured 0.1 ms faster per replay at 1 and 3
                                    // lanes, profiles/r04k_ab_lookahead_threshold.txt)
+constexpr int kFirstSplit = 64;    // first panels (fronts x lanes) from which a level's first panel runs as two
+                                   // launches (k_first_diag, k_first_trsm: higher occupancy) instead of one
+                                   // k_panel_first with in-launch hand-offs (16 / 256 / 1024 measured slower,
+                                   // profiles/r03j_ab_first_split_lookahead.txt; 32 / 128 within the replay
+                                   // noise, profiles/r04o_ab_knobs.txt, r06ae_knob_sweep.txt)
 constexpr int kMaxStampSlots = 256;  // PGO_STEP_STAMPS diagnostics // syrk tiles per step that ride inside k_step
 constexpr int kBwdRows = 512;      // rows per partial product of the backward solve
 // Schur-update tile tasks (front, row0 | clip << kClipShift, col0, k0): clip > 0
@@ -246,15 +251,25 @@ struct CholPlan {
   long long* d_xp_off = nullptr;   // (xp_loff, xp_lstride) pairs
   double* d_xprecv = nullptr;      // panel exchange: size regions of xp_rslot x batch doubles
   int* d_stepflag = nullptr;       // [batch][ns]: last panel (kb / 64 + 1) whose diagonal inverse is published
-  hipStream_t side = nullptr;      // look-ahead diagonal tiles
+  hipStream_t side = nullptr;      // the apart plain Schur tiles beside the panel chain
   hipStream_t side2 = nullptr;     // small fronts beside the blocked path
   hipStream_t side3 = nullptr;     // the second wavefront class of small fronts, beside side2
   hipStream_t side4 = nullptr;     // deferred far Schur updates (PanelStep::far_cnt)
   hipStream_t side5 = nullptr;     // a split step's column-block updates beside its diagonal tiles
-  hipStream_t side6 = nullptr;     // the m > 64 small-front classes narrower than kWaveW (PGO_WAVE_STREAMS)
-  hipEvent_t ev6 = nullptr;        // ... joined at the level's end
-  hipEvent_t fev[8] = {};          // their join events (ring)
-  hipEvent_t evs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t fev[8] = {};          // side4's join events (ring)
+  // chol_factor's fork / join events between the main stream and the side
+  // streams (each re-recorded per use; a wait sees the record before it)
+  enum {
+    kEvForkMain = 0,     // main -> side2 / side3 (a level's frontal vectors, its small fronts), -> side5 (a split step)
+    kEvJoinSide2 = 1,    // side2 -> main (frontal vectors; the small fronts at the level's end); side5 -> main (a split step)
+    kEvForkPlain = 2,    // main -> side / side4 ahead of a step's apart plain tiles; side -> main at the level's end
+    kEvPlainEven = 3,    // side -> main: the apart plain tiles of an even step, joined plain_lag steps later ...
+    kEvJoinSide3 = 4,    // side3 -> main (the m > 64 wavefront classes at the level's end)
+    kEvPlainOdd = 5,     // ... and of an odd step (a ring of two: ev_plain)
+    kEvCount = 6
+  };
+  static constexpr int ev_plain(size_t step) { return step & 1 ? kEvPlainOdd : kEvPlainEven; }
+  hipEvent_t evs[kEvCount] = {};
   int4 *d_bwd = nullptr, *d_bwd_part = nullptr, *d_bwdc = nullptr;
   int2* d_bwd_pref = nullptr;
   double* d_partial = nullptr;

@@ -48,7 +48,6 @@ struct CholDev {
   long long tfo;                   // Tinv + tfo: the inverses again, in the trsm's MFMA operand order
   int vst, xst, pst;               // fv, xv, backward partials per lane
   unsigned long long poll_ticks;   // in-launch hand-off: give up after this many 10 ns ticks
-  int diag_full;                   // PGO_DIAG_FULL=1 (A/B): diagonal tiles factored over all four 16-column blocks
 };
 
 // this workgroup's lane (blockIdx.y): every lane factors H + lambda_y I with
@@ -74,8 +73,6 @@ static CholDev dev_view(const CholPlan& P) {
   c.flag = P.d_flag;
   c.stepflag = P.d_stepflag;
   c.ns = P.ns;
-  static const int diag_full = getenv("PGO_DIAG_FULL") && atoi(getenv("PGO_DIAG_FULL")) == 1;
-  c.diag_full = diag_full;
   c.fst = P.ftotal;
   c.tst = 2 * P.ttotal;
   c.tfo = P.ttotal;
@@ -120,10 +117,7 @@ __device__ unsigned long long g_stamps[kMaxStampSlots][10];
 
 #ifdef PGO_DIAG_CLOCKS
 __device__ long long g_diag_clk[32];
-__device__ long long g_d8_clk[4][8][8];   // diag_factor_invert8: [wave][step][phase]
-__device__ int g_d8_dbg;   // diagnostics: 1 = waves 2-3 idle, 2 = no waits on wave 1, 4 = wave 1 idle
-#define D8_DBG(bit) (g_d8_dbg & (bit))
-#define DIAG_CLKF(q)                                                                   \
+#define DIAG_CLKF(q)                                                                  \
   do {                                                                                 \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                \
     __builtin_amdgcn_sched_barrier(0);                                                 \
@@ -131,18 +125,9 @@ __device__ int g_d8_dbg;   // diagnostics: 1 = waves 2-3 idle, 2 = no waits on w
     __builtin_amdgcn_sched_barrier(0);                                                 \
   } while (0)
 #define DIAG_CLK(q) if (threadIdx.x == 0 && blockIdx.x == 0) g_diag_clk[q] = clock64()
-#define D8_CLK(k, q)                                                                 \
-  do {                                                                               \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                              \
-    __builtin_amdgcn_sched_barrier(0);                                               \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x == 0) g_d8_clk[threadIdx.x >> 6][k][q] = clock64(); \
-    __builtin_amdgcn_sched_barrier(0);                                               \
-  } while (0)
 #else
 #define DIAG_CLK(q)
 #define DIAG_CLKF(q)
-#define D8_CLK(k, q)
-#define D8_DBG(bit) 0
 #endif
 
 
@@ -202,7 +187,6 @@ __device__ __forceinline__ void vec_assemble_body(const CholDev& c, int s, doubl
 // same launch, its frontal vectors (vec_assemble_body on the tile role's LDS
 // maps, fronts vfronts[b - ntile]): disjoint data (F / fv), one launch and no
 // side-stream fork and join per level
-template <int kUnroll>
 __global__ __launch_bounds__(256, 4) void k_assemble_tile(CholDev c, const int4* __restrict__ tasks,
                                                        const int2* __restrict__ iptr, const int* __restrict__ items,
                                                        const int4* __restrict__ pairs, const double* __restrict__ V,
@@ -317,28 +301,22 @@ __global__ __launch_bounds__(256, 4) void k_assemble_tile(CholDev c, const int4*
           val[u] = (row < mp && col < mp && row >= col) ? Fp[row + (size_t)j * ldp] : 0.0;
         }
       }
-      // the children's elements, in child order; kUnroll children's loads in
-      // flight together (the adds stay in child order: the same sums)
-      for (int k1 = 0; k1 < np; k1 += kUnroll) {
-        double add[kUnroll][kAsmGE];
-        bool in[kUnroll][kAsmGE];
+      // the children's elements, in child order; a child's kAsmGE loads in
+      // flight together
+      for (int kk = 0; kk < np; kk++) {
+        double add[kAsmGE];
+        bool in[kAsmGE];
+        const int a = rmap[kk][i];
+        const double* __restrict__ Fch = c.F + pbase[kk] + a;
 #pragma unroll
-        for (int x = 0; x < kUnroll; x++) {
-          const int kk = k1 + x;
-          const int a = kk < np ? rmap[kk][i] : -1;
-          const double* __restrict__ Fch = c.F + (kk < np ? pbase[kk] : 0) + a;
-#pragma unroll
-          for (int u = 0; u < kAsmGE; u++) {
-            const int b = a >= 0 ? cmap[kk][cg + 4 * (kAsmGE * g + u)] : -1;
-            in[x][u] = b >= 0 && b <= a;
-            add[x][u] = in[x][u] ? Fch[coff[kk][cg + 4 * (kAsmGE * g + u)]] : 0.0;
-          }
+        for (int u = 0; u < kAsmGE; u++) {
+          const int b = a >= 0 ? cmap[kk][cg + 4 * (kAsmGE * g + u)] : -1;
+          in[u] = b >= 0 && b <= a;
+          add[u] = in[u] ? Fch[coff[kk][cg + 4 * (kAsmGE * g + u)]] : 0.0;
         }
 #pragma unroll
-        for (int x = 0; x < kUnroll; x++)
-#pragma unroll
-          for (int u = 0; u < kAsmGE; u++)
-            if (in[x][u]) val[u] += add[x][u];
+        for (int u = 0; u < kAsmGE; u++)
+          if (in[u]) val[u] += add[u];
       }
 #pragma unroll
       for (int u = 0; u < kAsmGE; u++) {
@@ -346,98 +324,6 @@ __global__ __launch_bounds__(256, 4) void k_assemble_tile(CholDev c, const int4*
         if (row < mp && col < mp && row >= col) Fp[row + (size_t)j * ldp] = val[u];
       }
     }
-  }
-}
-
-// The previous form of the same assembly (scatter into an LDS tile, two barriers
-// per child rectangle), bitwise the same tile: PGO_ASM_PUSH=1 selects it (A/B)
-__global__ __launch_bounds__(256) void k_assemble_tile_push(CholDev c, const int4* __restrict__ tasks,
-                                                       const int2* __restrict__ iptr, const int* __restrict__ items,
-                                                       const int4* __restrict__ pairs, const double* __restrict__ V,
-                                                       const double* __restrict__ D,
-                                                       const double* __restrict__ lam_p) {
-  lane_offset(c);
-  __shared__ double T[64 * 65];
-  __shared__ int prow[64], pcol[64];
-  __shared__ long long ucol[64];   // the child's update-matrix columns: offset of (wc, wc + b0 + q) in its front
-  const int4 t = tasks[blockIdx.x];
-  const int p = t.x, mp = c.m[p];
-  const int R0 = 64 * (t.y >> 16), C0 = 64 * (t.y & 0xffff);
-  const int tid = threadIdx.x, r = tid & 63, cg = tid >> 6;
-  const double lam = lam_p[blockIdx.y];
-#pragma unroll
-  for (int u = 0; u < 16; u++) T[(tid & 63) + ((tid >> 6) + 4 * u) * 65] = 0.0;
-  __syncthreads();
-  const int2 it = iptr[blockIdx.x];
-  for (int q = tid; q < it.y; q += 256) {
-    const int code = items[it.x + q];
-    if (code >= 0) {
-      double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      for (int k = c.asm_ptr[code]; k < c.asm_ptr[code + 1]; k++) {
-        const double* v = V + 9 * (size_t)c.asm_src[k];   // element e at v[e]
-#pragma unroll
-        for (int e = 0; e < 9; e++) acc[e] += v[e];
-      }
-      const int i0 = 3 * c.asm_li[code] - R0, j0 = 3 * c.asm_lj[code] - C0;
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++)
-          if (i0 + a >= 0 && i0 + a < 64 && j0 + b >= 0 && j0 + b < 64) T[(i0 + a) + (j0 + b) * 65] = acc[3 * a + b];
-    } else {
-      const int j = ~code;
-      const double* d = D + 6 * (size_t)c.perm[j];
-      const int o = 3 * c.dg_loc[j];
-      const double dv[6] = {d[0] + lam, d[1], d[2], d[3] + lam, d[4], d[5] + lam};   // (0,0) (1,0) (2,0) (1,1) (2,1) (2,2)
-      const int ia[6] = {0, 1, 2, 1, 2, 2}, ib[6] = {0, 0, 0, 1, 1, 2};
-#pragma unroll
-      for (int e = 0; e < 6; e++) {
-        const int i = o + ia[e] - R0, jj = o + ib[e] - C0;
-        if (i >= 0 && i < 64 && jj >= 0 && jj < 64) T[i + jj * 65] = dv[e];
-      }
-    }
-  }
-  for (int k = 0; k < t.w; k++) {
-    const int4 q = pairs[t.z + k];
-    const int ch = q.x, a0 = q.y, b0 = q.z, nr = q.w & 0xff, nc = q.w >> 8;
-    const int mc = c.m[ch], wc = c.w[ch];
-    const int* __restrict__ rel = c.ea_rel + c.ea_ptr[ch];
-    __syncthreads();   // the H entries / the previous child's adds are done, prow / pcol reusable
-    if (tid < nr) {
-      const int a = a0 + tid;
-      prow[tid] = 3 * rel[a / 3] + a % 3 - R0;
-    } else if (tid >= 64 && tid - 64 < nc) {
-      const int b = b0 + tid - 64;
-      pcol[tid - 64] = (3 * rel[b / 3] + b % 3 - C0) * 65;
-    } else if (tid >= 128 && tid - 128 < nc) {
-      ucol[tid - 128] = fcol_off(mc, front_packed(mc, wc), wc + b0 + tid - 128) + wc;
-    }
-    __syncthreads();
-    if (r >= nr) continue;
-    const int a = a0 + r;
-    const double* __restrict__ Fch = c.F + c.foff[ch] + a;
-    constexpr int R = 16;
-    double v[R];
-#pragma unroll
-    for (int j = 0; j < R; j++) {
-      const int bb = cg + 4 * j;
-      v[j] = (bb < nc && b0 + bb <= a) ? Fch[ucol[bb]] : 0.0;
-    }
-    const int pr = prow[r];
-#pragma unroll
-    for (int j = 0; j < R; j++) {
-      const int bb = cg + 4 * j;
-      if (bb < nc && b0 + bb <= a) T[pr + pcol[bb]] += v[j];
-    }
-  }
-  __syncthreads();
-  const bool pkp = front_packed(mp, c.w[p]);
-  double* __restrict__ Fp = fcol(c.F + c.foff[p], mp, pkp, C0);   // the tile's columns: one column block
-  const int ldp = fld(mp, pkp, C0);
-#pragma unroll
-  for (int u = 0; u < 16; u++) {
-    const int i = tid & 63, j = (tid >> 6) + 4 * u, row = R0 + i, col = C0 + j;
-    if (row < mp && col < mp && row >= col) Fp[row + (size_t)j * ldp] = T[i + j * 65];
   }
 }
 
@@ -913,21 +799,18 @@ __device__ __forceinline__ void front_wave_body(const CholDev& c, int s, double*
   DIAG_CLK(28);
 }
 
-// Small front with 64 < m <= 64 NW rows and w <= W (16 or 32) pivot columns,
-// by NW wavefronts: wave q holds rows [64 q, 64 q + 64) of the m x w panel in
+// Small front with 64 < m <= 128 rows and w <= W pivot columns, by two
+// wavefronts: wave q holds rows [64 q, 64 q + 64) of the m x w panel in
 // registers (thread t: row t) -- half the registers of one wave holding two
 // rows per lane -- and the trailing update's 16-column blocks are dealt to the
 // waves.  The pivot steps are front_wave_body's blocked form, with workgroup
 // barriers where its LDS hand-offs cross the waves; every element sees the
-// same fma's in the same order: bitwise front_wave_body's front.  NW = 4
-// (round 4): 128 < m <= 256, fronts stored packed (pgo_chol.h front_packed:
-// the panel's columns lie in the first 64-column block, the trailing columns
-// are addressed by their block), which the blocked path took before.
-template <int W, int NW = 2>
+// same fma's in the same order: bitwise front_wave_body's front.
+template <int W>
 __device__ __forceinline__ void front_wave2_body(const CholDev& c, int s, double* S) {
-  constexpr int LDP = W + 1;
+  constexpr int LDP = W + 1, NW = 2;   // NW: the wavefronts
   const int m = c.m[s], w = c.w[s];
-  const bool pk = front_packed(m, w);
+  const bool pk = front_packed(m, w);   // (false for every front the planner sends here: m <= kSmallFront, w <= kWaveW)
   const int ld0 = fld(m, pk, 0);  // the panel's columns (the first column block when packed)
   double* PR = S;                 // m x W row-major copy of L (after the factorisation)
   double* cb = S + m * LDP;       // the diagonal block's rows and v (8 x 9)
@@ -1088,13 +971,7 @@ template <int W>
 __global__ __launch_bounds__(128) void k_front_wave2(CholDev c, const int* __restrict__ list) {
   lane_offset(c);
   extern __shared__ __attribute__((aligned(16))) double S[];
-  front_wave2_body<W, 2>(c, list[blockIdx.x], S);
-}
-template <int W>
-__global__ __launch_bounds__(256) void k_front_wave4(CholDev c, const int* __restrict__ list) {
-  lane_offset(c);
-  extern __shared__ __attribute__((aligned(16))) double S[];
-  front_wave2_body<W, 4>(c, list[blockIdx.x], S);
+  front_wave2_body<W>(c, list[blockIdx.x], S);
 }
 
 template <int W, bool kTwoRows>
@@ -1134,101 +1011,6 @@ __device__ __forceinline__ void st16(double* C, d4 v, bool sub) {
   }
 }
 
-// In place L -> L^-1 (8x8 lower, packed), columns right to left:
-// X_ij = -(1 / L_jj) sum_{k=j+1..i} X_ik L_kj.
-__device__ __forceinline__ void inv8_lane(double (&a)[36], const double (&iv)[8]) {
-#pragma unroll
-  for (int j = 7; j >= 0; j--) {
-#pragma unroll
-    for (int i = 7; i > j; i--) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = i; k > j; k--) s = fma(a[P8(i, k)], a[P8(k, j)], s);   // X_i,j+1 (newest) last
-      a[P8(i, j)] = -iv[j] * s;
-    }
-    a[P8(j, j)] = iv[j];
-  }
-}
-
-// Factor and inverse of the 16x16 diagonal block TJ (LDS, ld 65, lower valid)
-// by one wave, as 2x2 blocks of 8: A11 = L11 L11^T and X11 = L11^-1 lane-local
-// (chol8_lane, inv8_lane, every lane the same values), L21 = A21 X11^T and
-// A22 - L21 L21^T one element per lane, A22' lane-local again, then
-// X21 = -X22 (L21 X11).  Writes L21 to TJ (the 8x8 diagonal blocks of L are
-// not stored: round 5, nothing reads a diagonal tile's L) and X to WJ (ld 65,
-// lower, zeros above); sc: LDS scratch of 64.  Same wave only: LDS accesses of one
-// wave complete in order, so no barrier between a lane's store and another's
-// load.  (Solving rows of L21 against a lane-held L11 instead, with A22' formed
-// in registers, measured slower: 34.4 k against 33.0 k cycles per 64x64.)
-__device__ __forceinline__ bool diag16_lane(double* TJ, double* WJ, double* sc) {
-  const int l = threadIdx.x & 63, r = l >> 3, c = l & 7;
-  double a[36], iv[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) a[P8(i, j)] = TJ[i + j * 65];
-  // zeros above the diagonal of X (blocks (0,0), (1,1) upper, (0,1))
-  WJ[r + (8 + c) * 65] = 0.0;
-  if (c > r) {
-    WJ[r + c * 65] = 0.0;
-    WJ[(8 + r) + (8 + c) * 65] = 0.0;
-  }
-  DIAG_CLK(13);
-  bool bad = chol8_lane(a, iv);
-  DIAG_CLK(14);
-  inv8_lane(a, iv);   // (L11 itself is not stored: nothing reads a diagonal block's L, see store_factor)
-  DIAG_CLK(15);
-  if (l == 0) {
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-      for (int j = 0; j <= i; j++) WJ[i + j * 65] = a[P8(i, j)];
-  }
-  __builtin_amdgcn_wave_barrier();
-  // L21 (r, c) = sum_k A21(r, k) X11(c, k)   (X11 upper is zero)
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) s = fma(TJ[(8 + r) + k * 65], WJ[c + k * 65], s);
-  __builtin_amdgcn_wave_barrier();
-  TJ[(8 + r) + c * 65] = s;
-  __builtin_amdgcn_wave_barrier();
-  // A22 (r, c) -= sum_k L21(r, k) L21(c, k), lower part
-  double t = TJ[(8 + r) + (8 + c) * 65];
-#pragma unroll
-  for (int k = 0; k < 8; k++) t = fma(-TJ[(8 + r) + k * 65], TJ[(8 + c) + k * 65], t);
-  // Y = L21 X11 (X11 (k, c) zero for k < c)
-  double y = 0.0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) y = fma(TJ[(8 + r) + k * 65], WJ[k + c * 65], y);
-  __builtin_amdgcn_wave_barrier();
-  if (c <= r) TJ[(8 + r) + (8 + c) * 65] = t;
-  sc[r * 8 + c] = y;
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i = 0; i < 8; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) a[P8(i, j)] = TJ[(8 + i) + (8 + j) * 65];
-  DIAG_CLK(16);
-  bad = chol8_lane(a, iv) || bad;
-  DIAG_CLK(17);
-  inv8_lane(a, iv);   // (nor L22)
-  if (l == 0) {
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-      for (int j = 0; j <= i; j++) WJ[(8 + i) + (8 + j) * 65] = a[P8(i, j)];
-  }
-  __builtin_amdgcn_wave_barrier();
-  DIAG_CLK(18);
-  // X21 (r, c) = -sum_k X22 (r, k) Y (k, c)   (X22 upper is zero)
-  double z = 0.0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) z = fma(WJ[(8 + r) + (8 + k) * 65], sc[k * 8 + c], z);
-  WJ[(8 + r) + c * 65] = -z;
-  DIAG_CLK(19);
-  return bad;
-}
-
 // x = L^-1 x in place, L an 8x8 lower block held whole in every lane (packed,
 // iv[k] = 1 / L_kk): the forward substitution of one right-hand side per lane
 __device__ __forceinline__ void fwd8_lane(const double (&a)[36], const double (&iv)[8], double (&x)[8]) {
@@ -1241,15 +1023,20 @@ __device__ __forceinline__ void fwd8_lane(const double (&a)[36], const double (&
   }
 }
 
-// diag16_lane's factor and inverse with the lane-redundant work cut to the two
-// 8x8 factors (round 6).  Every other piece is one forward substitution per
+// Factor and inverse of the 16x16 diagonal block TJ (LDS, ld 65, lower valid)
+// by one wave, as 2x2 blocks of 8: A11 = L11 L11^T and A22' = A22 - L21 L21^T
+// are factored lane-local (chol8_lane, every lane the same values) -- the only
+// lane-redundant work.  Every other piece is one forward substitution per
 // lane against the lane-held L11 / L22 -- lanes 0-7 one right-hand side e_c
 // each (a column of X11 / X22), lanes 8-15 a row of A21 (-> a row of L21) /
 // a column of -Y (-> a column of X21 = -X22 Y, Y = L21 X11) -- in the same
-// instructions, instead of inv8_lane's lane-redundant inverse and its lane-0
-// stores (36 each) and the L21 / X21 products through LDS.  Same outputs as
-// diag16_lane (L21 in TJ, X lower in WJ with zeros above); a different
-// operation order, so not bitwise its result (the oracle tolerances hold).
+// instructions.  Writes L21 to TJ (the 8x8 diagonal blocks of L are not
+// stored: nothing reads a diagonal tile's L, see store_factor) and X to WJ
+// (ld 65, lower, zeros above); sc: LDS scratch of 64.  Same wave only: LDS
+// accesses of one wave complete in order, so no barrier between a lane's store
+// and another's load.  (Round 5's form, a lane-redundant 8x8 inverse with
+// lane-0 stores and the L21 / X21 products through LDS, is retired:
+// DESIGN.md, Retired experiments.)
 __device__ __forceinline__ bool diag16_fs(double* TJ, double* WJ, double* sc) {
   const int l = threadIdx.x & 63, r = l >> 3, c = l & 7;
   double a[36], iv[8], x[8];
@@ -1304,7 +1091,7 @@ __device__ __forceinline__ bool diag16_fs(double* TJ, double* WJ, double* sc) {
 // Cholesky factor L and inverse X = L^-1 of the 64x64 SPD tile T (LDS,
 // column-major, ld 65, lower part valid, identity beyond the live size), by the
 // 4 waves of the workgroup: right-looking over 16-column blocks J; the 16x16
-// diagonal block is factored and inverted by wave 0 (diag16_lane), the rest
+// diagonal block is factored and inverted by wave 0 (diag16_fs), the rest
 // are 16x16x16 MFMA products:
 //   L_IJ = A_IJ X_JJ^T,  X_JK = X_JJ W_JK (K < J),
 //   A_IK -= L_IJ L_KJ^T (K > J),  W_IK -= L_IJ X_JK (K <= J)
@@ -1318,7 +1105,6 @@ __device__ __forceinline__ bool diag16_fs(double* TJ, double* WJ, double* sc) {
 // element sees the same operations as with all four blocks, the callers read
 // only the live part of L and X.
 // Returns (wave 0) whether a pivot was not positive and finite.
-template <bool kFS = true>   // kFS: diag16_fs (round 6), else diag16_lane
 __device__ __forceinline__ bool diag_factor_invert(double* T, double* W, double* bc, int nbl = 64) {
   const int tid = threadIdx.x, wv = tid >> 6;
   const int Jn = (nbl + 15) >> 4;   // live 16-column blocks (1..4)
@@ -1333,7 +1119,7 @@ __device__ __forceinline__ bool diag_factor_invert(double* T, double* W, double*
         st16(TJ, v, true);
         __builtin_amdgcn_wave_barrier();
       }
-      bad = (kFS ? diag16_fs(TJ, W + o + o * 65, bc) : diag16_lane(TJ, W + o + o * 65, bc)) || bad;
+      bad = diag16_fs(TJ, W + o + o * 65, bc) || bad;
     }
     __syncthreads();
     DIAG_CLK(1 + 3 * J);
@@ -1391,312 +1177,10 @@ __device__ __forceinline__ bool diag_factor_invert(double* T, double* W, double*
   return bad;
 }
 
-// ---- diagonal tile in 8-column steps on four concurrent waves (round 6) ----
-// The same output as diag_factor_invert -- X = L^-1 of the 64x64 SPD tile T
-// (LDS, ld 65, lower valid, identity past the live size nbl) into W (ld 65,
-// zeros on entry, lower X, zeros above) -- with the pivot chain cut to what
-// one wave must do in sequence: eight lane-redundant 8x8 factors (chol8_lane)
-// and, between them, two short element-parallel phases.  Everything else runs
-// beside the chain on the other waves, synchronised by LDS flags (workgroup
-// scope release / acquire, no s_barrier per step):
-//   wave 0 (the chain), step k (kb = 8k): A_kk (final) -> chol8_lane -> each
-//     lane i >= kb+8 solves its row of block column k against the lane-held
-//     L_kk (x_i = a_i L_kk^-T; stored transposed in T's strict upper part, at
-//     T[(kb + q) + 65 i], where row i's eight values are contiguous) -> the
-//     next diagonal block A_{k+1,k+1} -= L_{k+1,k} L_{k+1,k}^T one element per
-//     lane -> flag PANEL = k + 1;
-//   wave 1 (trailing updates, v_mfma_f64_16x16x4f64 tiles): after PANEL > k,
-//     panel k onto block column k+1 below its diagonal block (flag T1A), then
-//     onto the tile column from block k+2 (flag T1B: blocks k+2, k+3, what the
-//     chain's next two steps read), then the rest;
-//   waves 2 and 3 (the inverse, by 8-row blocks of parity p): X_ss =
-//     inv8(chol8(A_ss)) in registers for s = p mod 2, S_i += L_{i,s-1} X_{s-1}
-//     (MFMA, into W) for the wave's row blocks i >= s once row block s-1 of X
-//     is final (flag XDONE), then row block s of X = -X_ss [S_s | -I] (flag
-//     XDONE = s + 1).
-// Every element of T and W has one writer per update and sees its updates in
-// panel order (the flags order the writers), every sum has a fixed order: the
-// result does not depend on the waves' timing.  A flag wait gives up after a
-// bounded spin (never expected) and reports it as bit 2 of the return value,
-// which the callers OR into the pivot flag (the host's hand-off timeout path).
-namespace d8f {
-constexpr int PANEL = 0, T1A = 1, T1B = 2, XDONE = 3, ERR = 4;
-}
-// signal: this wave's LDS writes have completed (lgkmcnt(0); the LDS is
-// coherent across the CU), then the flag store.  wait: poll the flag (the
-// loads after it are issued only once it is seen); no global-memory fence --
-// the flags order LDS traffic only.
-__device__ __forceinline__ void lds_signal(int* fl, int which, int v) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  *reinterpret_cast<volatile int*>(fl + which) = v;
-}
-__device__ __forceinline__ void lds_wait(int* fl, int which, int v) {
-  int n = 0;
-  while (*reinterpret_cast<volatile int*>(fl + which) < v) {
-    if (++n > (1 << 21)) {   // ~0.1 s: a lost signal must never hang the GPU
-      *reinterpret_cast<volatile int*>(fl + d8f::ERR) = 1;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  asm volatile("" ::: "memory");
-}
-
-// D(16x16) = sum_{q < 8} A(row, q) B(q, col) on one wave, operands read from
-// LDS by row: A(row, q) = Ar[row][q0 + q], B(q, col) = Bc[col][q0 + q] with
-// rows at pa(row), pb(col) (ld 65 "transposed" storage: element q of row r at
-// base[q + 65 r]); D in the f64 MFMA layout (lane l, reg r -> row (l >> 4) + 4r,
-// col l & 15); acc holds the initial values
-__device__ __forceinline__ d4 mm16x8(const double* A, const double* B, int q0, int ra, int rb, d4 acc) {
-  const int l = threadIdx.x & 63, kq = l >> 4;
-#pragma unroll
-  for (int u = 0; u < 2; u++) {
-    const double a = A[(q0 + 4 * u + kq) + 65 * ra];
-    const double b = B[(q0 + 4 * u + kq) + 65 * rb];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// trailing tiles on wave 1, up to 3 per call: T[R + row][C + col] -= sum_q
-// L[R + row][kb + q] L[C + col][kb + q] for row + R < nbl, col + C < cend and
-// (lower) R + row >= C + col.  Every tile's LDS loads (operands and C) are
-// issued first, then the MFMAs, then the stores: one LDS latency per call
-// instead of three per tile.
-__device__ __forceinline__ void d8_trail3(double* T, int kb, const int (&R)[3], const int (&C)[3], int nt, int nbl,
-                                          int cend, bool lower) {
-  // Branch-free: an element outside the region reads and writes the lane's own
-  // slot in T's padding row (T[64 + 65 l]: ld 65, rows 0..63 used), so no load
-  // or store needs an EXEC mask of its own (measured: the per-element masks cost
-  // more than the MFMAs, profiles/r06*_ubench_factor64.txt)
-  const int l = threadIdx.x & 63, kq = l >> 4, li = l & 15;
-  double a[3][2], b[3][2], cv[3][4];
-  int ad[3][4];
-#pragma unroll
-  for (int t = 0; t < 3; t++) {
-    if (t >= nt) break;   // (wave-uniform)
-    const int ra = min(R[t] + li, 63), rb = min(C[t] + li, 63);
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      a[t][u] = T[(kb + 4 * u + kq) + 65 * ra];
-      b[t][u] = T[(kb + 4 * u + kq) + 65 * rb];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int i = R[t] + kq + 4 * r, j = C[t] + li;
-      ad[t][r] = (i < nbl && j < cend && (!lower || i >= j)) ? i + 65 * j : 64 + 65 * l;
-      cv[t][r] = T[ad[t][r]];
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 3; t++) {
-    if (t >= nt) break;
-    d4 acc = {0, 0, 0, 0};
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][0], b[t][0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t][1], b[t][1], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; r++) T[ad[t][r]] = cv[t][r] - acc[r];
-  }
-}
-
-__device__ __forceinline__ int diag_factor_invert8(double* T, double* W, double* bc, int nbl = 64) {
-  const int tid = threadIdx.x, l = tid & 63;
-  // roles by wave: 0 the chain, 1 the trailing updates, 2-3 the inverse
-  // (diagnostics bit 8: the trailing updates on wave 2, the inverse on waves 1, 3)
-  const int wv = D8_DBG(8) ? ((tid >> 6) == 1 ? 2 : (tid >> 6) == 2 ? 1 : (tid >> 6)) : tid >> 6;
-  int* fl = reinterpret_cast<int*>(bc);
-  const int K = (nbl + 7) >> 3;   // live 8-column steps
-  if (tid < 8) fl[tid] = 0;
-  __syncthreads();
-  DIAG_CLK(0);
-  int ret = 0;
-  if (wv == 0) {   // ---------------- the pivot chain
-    for (int k = 0; k < K; k++) {
-      const int kb = 8 * k;
-      double a[36], iv[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) a[P8(i, j)] = T[(kb + i) + 65 * (kb + j)];
-      D8_CLK(k, 0);
-      if (chol8_lane(a, iv)) ret |= 1;
-      D8_CLK(k, 1);
-      if (k == K - 1) break;
-      if (!D8_DBG(2)) lds_wait(fl, d8f::T1A, k);   // block column k through panel k-1 (wave 1)
-      D8_CLK(k, 2);
-      const int i = l;
-      if (i >= kb + 8 && i < nbl) {   // row i of block column k: x = a L_kk^-T
-        double x[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) x[c] = T[i + 65 * (kb + c)];
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-          double s = x[c];
-#pragma unroll
-          for (int t = 0; t < c; t++) s = fma(-a[P8(c, t)], x[t], s);
-          x[c] = s * iv[c];
-        }
-#pragma unroll
-        for (int c = 0; c < 8; c++) T[(kb + c) + 65 * i] = x[c];
-      }
-      __builtin_amdgcn_wave_barrier();
-      D8_CLK(k, 3);
-      if (!D8_DBG(2)) lds_wait(fl, d8f::T1B, k);   // the next diagonal block through panel k-1 (wave 1)
-      D8_CLK(k, 4);
-      {   // A_{k+1,k+1} -= L_{k+1,k} L_{k+1,k}^T, lane (r, c), r >= c
-        const int r = l >> 3, c = l & 7, ii = kb + 8 + r, jj = kb + 8 + c;
-        if (c <= r && ii < nbl) {
-          double t = T[ii + 65 * jj];
-#pragma unroll
-          for (int q = 0; q < 8; q++) t = fma(-T[(kb + q) + 65 * ii], T[(kb + q) + 65 * jj], t);
-          T[ii + 65 * jj] = t;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      lds_signal(fl, d8f::PANEL, k + 1);
-      D8_CLK(k, 5);
-    }
-    DIAG_CLK(1);
-  } else if (wv == 1) {   // ---------------- trailing updates
-    for (int k = 0; k + 1 < K && !D8_DBG(4); k++) {
-      const int kb = 8 * k;
-      lds_wait(fl, d8f::PANEL, k + 1);
-      D8_CLK(k, 0);
-      const int nt = (nbl - kb - 16 + 15) >> 4;   // 16-row tiles below the next diagonal block (<= 3)
-      {
-        const int R[3] = {kb + 16, kb + 32, kb + 48}, C[3] = {kb + 8, kb + 8, kb + 8};
-        d8_trail3(T, kb, R, C, nt, nbl, min(kb + 16, nbl), false);
-      }
-      lds_signal(fl, d8f::T1A, k + 1);
-      D8_CLK(k, 1);
-      {
-        const int R[3] = {kb + 16, kb + 32, kb + 48}, C[3] = {kb + 16, kb + 16, kb + 16};
-        d8_trail3(T, kb, R, C, nt, nbl, nbl, true);
-      }
-      lds_signal(fl, d8f::T1B, k + 1);
-      D8_CLK(k, 2);
-      {   // the rest: tile columns from kb + 32 (<= 3 tiles)
-        int R[3] = {0, 0, 0}, C[3] = {0, 0, 0}, n = 0;
-        for (int c0 = kb + 32; c0 < nbl; c0 += 16)
-          for (int r0 = c0; r0 < nbl; r0 += 16)
-            if (n < 3) {
-              R[n] = r0;
-              C[n] = c0;
-              n++;
-            }
-        d8_trail3(T, kb, R, C, n, nbl, nbl, true);
-      }
-      D8_CLK(k, 3);
-    }
-  } else {   // ---------------- the inverse, row blocks of parity p
-    const int p = wv - 2;
-    for (int s = 0; s < K && !D8_DBG(1); s++) {
-      const int sb = 8 * s;
-      lds_wait(fl, d8f::PANEL, s);   // A_ss final, panels < s written
-      D8_CLK(s, 0);
-      double xs[36], iv[8];
-      const bool mine = (s & 1) == p;
-      if (mine) {   // X_ss = L_ss^-1, lane-redundant (the chain's own factor of the same A_ss)
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) xs[P8(i, j)] = T[(sb + i) + 65 * (sb + j)];
-        chol8_lane(xs, iv);
-        inv8_lane(xs, iv);
-      }
-      D8_CLK(s, 1);
-      if (s >= 1) {   // S_i += L_{i,s-1} X_{s-1} for my row blocks i >= s
-        lds_wait(fl, d8f::XDONE, s);
-        D8_CLK(s, 2);
-        const int tb = sb - 8;                       // X_{s-1}: rows tb.., columns < sb
-        const int i0 = s + (((s & 1) == p) ? 0 : 1);  // my first row block >= s
-        const int nr = i0 < K ? 8 * ((K - i0 + 1) >> 1) : 0;   // stacked rows (8 per block)
-        // tiles (stacked 16-row tile, 16-column tile), up to 8, four per batch:
-        // every load of a batch first, then its MFMAs, then its stores
-        const int nrt = (nr + 15) >> 4, nct = (sb + 15) >> 4, ntile = nrt * nct;
-        const int kq = l >> 4, li = l & 15;
-        for (int t0 = 0; t0 < ntile; t0 += 4) {
-          double av[4][2], bv[4][2];
-          d4 acc[4];
-          int wad[4][4];
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            if (t0 + t >= ntile) break;   // (wave-uniform)
-            const int R = 16 * ((t0 + t) / nct), C = 16 * ((t0 + t) % nct);
-            const int rr = R + li;                                                   // A operand's stacked row
-            const int ra = min(8 * (i0 + 2 * (rr >> 3)) + (rr & 7), 63);
-            const int cb = min(C + li, 63);                                          // B operand's column
-            // A(row, q) = L[ra][tb + q] = T[(tb + q) + 65 ra]; B(q, col) = X[tb + q][cb] = W[(tb + q) + 65 cb]
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-              av[t][u] = T[(tb + 4 * u + kq) + 65 * ra];
-              bv[t][u] = W[(tb + 4 * u + kq) + 65 * cb];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {   // S so far (zeros before the first update); outside: the padding slot
-              const int ro = R + kq + 4 * r, blk = i0 + 2 * (ro >> 3), row = 8 * blk + (ro & 7), col = C + li;
-              wad[t][r] = (ro < nr && blk < K && col < sb && row < nbl) ? row + 65 * col : 64 + 65 * l;
-              acc[t][r] = W[wad[t][r]];
-            }
-          }
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            if (t0 + t >= ntile) break;
-#pragma unroll
-            for (int u = 0; u < 2; u++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t][u], bv[t][u], acc[t], 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; r++) W[wad[t][r]] = acc[t][r];
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-      D8_CLK(s, 3);
-      if (mine) {   // row block s of X: -X_ss [S_s | -I], lane = column
-        const int col = l;
-        if (col < sb + 8) {
-          double sv[8];
-#pragma unroll
-          for (int q = 0; q < 8; q++) sv[q] = col < sb ? W[(sb + q) + 65 * col] : (q == col - sb ? -1.0 : 0.0);
-#pragma unroll
-          for (int r = 0; r < 8; r++) {
-            double o = 0.0;
-#pragma unroll
-            for (int q = 0; q <= r; q++) o = fma(xs[P8(r, q)], sv[q], o);
-            W[sb + r < nbl ? (sb + r) + 65 * col : 64 + 65 * l] = -o;   // (outside: the padding slot)
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-        lds_signal(fl, d8f::XDONE, s + 1);
-        D8_CLK(s, 4);
-      }
-    }
-  }
-  __syncthreads();
-  DIAG_CLK(12);
-  if (fl[d8f::ERR]) ret |= 2;
-  return ret;
-}
-
-// The diagonal tiles' factor + inverse, chosen at build time (one form per
-// library keeps k_step's code and registers to that form; A/B builds:
-// `make -C graphslam_amd/csrc ab-forms` -> graphslam_amd/build/libpgo_form<N>.so,
-// loaded with PGO_LIB_PATH): 1 diag_factor_invert over diag16_fs (default,
-// round 6), 0 over diag16_lane (round 5), 2 diag_factor_invert8 (8-column steps
-// on four concurrent waves; measured slower, profiles/r06*_ubench_factor64.txt)
-#ifndef PGO_DIAG_FORM
-#define PGO_DIAG_FORM 1
-#endif
-// the diagonal tile's factor + inverse by the configured form; a pivot that is
-// not positive and finite (bit 1) or a lost LDS flag (bit 2: the host's
-// hand-off timeout path) goes to the lane's pivot flag
+// the diagonal tile's factor + inverse (live size nb); a pivot that is not
+// positive and finite goes to the lane's pivot flag (bit 1)
 __device__ __forceinline__ void factor_invert_tile(const CholDev& c, double* Ts, double* Ws, double* bc, int nb) {
-  const int nbl = c.diag_full ? 64 : nb;
-#if PGO_DIAG_FORM == 2
-  const int r = diag_factor_invert8(Ts, Ws, bc, nbl);
-#else
-  const int r = diag_factor_invert<PGO_DIAG_FORM != 0>(Ts, Ws, bc, nbl) ? 1 : 0;
-#endif
-  if (r) __hip_atomic_fetch_or(c.flag, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (diag_factor_invert(Ts, Ws, bc, nb)) __hip_atomic_fetch_or(c.flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- in-launch hand-off of a diagonal tile's inverse (MI355X_MICROARCH.md,
@@ -1801,8 +1285,8 @@ __device__ __forceinline__ void publish_inverse(double* __restrict__ Mf, const d
 // tile's own L_bb is not written back to the front (round 5): every later
 // reader of a diagonal tile uses its inverse (the column solves' operand copy,
 // the backward solve and the marginals M, the panel exchange) and reads L
-// only below the tile, so those stores and the diagonal blocks' lane-0 stores
-// in diag16_lane were dead (the front keeps the assembled values there).
+// only below the tile, so those stores were dead (the front keeps the
+// assembled values there).
 __device__ __forceinline__ void store_factor(double* __restrict__ M, const double* Ws, int nb) {
   const int tid = threadIdx.x;
   for (int idx = tid; idx < 4096; idx += 256) {
@@ -1952,7 +1436,8 @@ __device__ __forceinline__ void trsm_rows(const CholDev& c, int s, int r0, int k
 // from global (the panel columns are L2-resident); the product is formed
 // transposed (A = column-side rows) so each store covers 16 consecutive rows.
 // Inner tasks (bit 31 of k0) clip columns at the end of the current kKB block.
-template <bool kToLds>
+// The updated tile is also left in Ts (LDS, ld 65) for the column solve that
+// follows in the same workgroup (k_step).
 __device__ __forceinline__ void syrk_tile64(const CholDev& c, const int4 t, int kb, double* Ts) {
   const int s = t.x, row0 = t.y, col0 = t.z;
   const bool inner = t.w < 0;
@@ -2013,19 +1498,14 @@ __device__ __forceinline__ void syrk_tile64(const CholDev& c, const int4 t, int 
         if (row < m && col < colend && row >= col) {
           const double v = cold[mi][mj][r] - a[r];
           Cb[row + (size_t)(col - col0) * ldc] = v;
-          if (kToLds) Ts[(row - row0) + (col - col0) * 65] = v;
+          Ts[(row - row0) + (col - col0) * 65] = v;
         }
       }
     }
 }
 
-// register-fragment variant (kept for the microbenchmark; k_panel_syrk_lds is launched)
-__global__ __launch_bounds__(256) void k_panel_syrk(CholDev c, const int4* __restrict__ tasks, int kb) {
-  lane_offset(c);
-  syrk_tile64<false>(c, tasks[blockIdx.x], kb, nullptr);
-}
-
-// Same tile and semantics as k_panel_syrk, with the panel rows and columns of
+// Same tile and semantics as syrk_tile64 (task (front, row0 | clip << kClipShift,
+// col0, k0); nothing left in LDS), with the panel rows and columns of
 // the tile staged through LDS in chunks of 16 k (double-buffered, every operand
 // loaded once per workgroup instead of once per wave pair; 8 loads per thread
 // per chunk, issued one chunk ahead of the MFMAs).  Low register count, so
@@ -2034,7 +1514,7 @@ __global__ __launch_bounds__(256) void k_panel_syrk(CholDev c, const int4* __res
 // KC: panel columns staged per chunk (16; 32 halves the round trips with the
 // same 4-deep MFMA steps in the same k order -- bitwise the same tile -- but
 // measured no faster, profiles/r05n_syrk_ubench.txt)
-template <bool kPrefC = false, int KC = 16>   // kPrefC: the C tile's loads issued before the k loop
+template <int KC = 16>
 __device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, int kb, double* smem) {
   constexpr int LD = 64 + 4, NQ = KC / 4;
   double(*Sr)[KC * LD] = reinterpret_cast<double(*)[KC * LD]>(smem);
@@ -2098,7 +1578,6 @@ __device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, in
         cold[p][h] = (active && row < m && col < colend && row >= col) ? Cb[row + (size_t)(col - col0) * ldc] : 0.0;
       }
   };
-  if (kPrefC) load_c();
   load(0);
   stash(0);
   __syncthreads();
@@ -2125,7 +1604,9 @@ __device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, in
     __syncthreads();
   }
   if (!active) return;
-  if (!kPrefC) load_c();
+  // (the C tile's loads after the k loop: issued before it, 117 vs 110 us on
+  // the 4096-row outer update, profiles/r04g_syrk_ubench.txt)
+  load_c();
 #pragma unroll
   for (int p = 0; p < 8; p++)
 #pragma unroll
@@ -2139,12 +1620,6 @@ __global__ __launch_bounds__(256) void k_panel_syrk_lds(CholDev c, const int4* _
   lane_offset(c);
   __shared__ __attribute__((aligned(16))) double smem[4 * 16 * 68];
   syrk_lds_body(c, tasks[blockIdx.x], kb, smem);
-}
-// (the C-prefetch form, for the microbenchmark A/B: scripts/ubench_syrk.hip)
-__global__ __launch_bounds__(256) void k_panel_syrk_lds_pc(CholDev c, const int4* __restrict__ tasks, int kb) {
-  lane_offset(c);
-  __shared__ __attribute__((aligned(16))) double smem[4 * 16 * 68];
-  syrk_lds_body<true>(c, tasks[blockIdx.x], kb, smem);
 }
 
 // Schur update of a diagonal 64x64 tile into LDS: Ts (ld 65, lower) = C - P P^T,
@@ -2457,7 +1932,7 @@ __global__ __launch_bounds__(256, 2) void k_step(CholDev c, const int4* __restri
     const int sl = b == nsd && blockIdx.y == 0 ? slot : -1;
     STAMP(sl, 5);
     const int4 t = col[b - nsd];   // (front, r0, kn, kb)
-    syrk_tile64<true>(c, t, kb, smem);
+    syrk_tile64(c, t, kb, smem);
     __syncthreads();
     STAMP(sl, 6);
     const int s = t.x, kn = t.z, nb = min(kNB, c.w[s] - kn);
@@ -2484,7 +1959,7 @@ __global__ __launch_bounds__(256, 2) void k_step_diag(CholDev c, const int4* __r
 }
 
 // Schur update of one 128x128 lower tile (same task format and semantics as
-// k_panel_syrk).  The panel rows/columns are staged through LDS in chunks of
+// k_panel_syrk_lds).  The panel rows/columns are staged through LDS in chunks of
 // 16 k (double-buffered: the global loads of chunk c+1 are in flight while the
 // MFMAs of chunk c run); each wave owns 64x64 of the tile as 4x4
 // v_mfma_f64_16x16x4_f64 blocks.
@@ -3347,44 +2822,17 @@ static int step_split_threshold() {
 hipError_t chol_upload(CholPlan& P, hipStream_t s) {
   CH_TRY(upload_index(P, s));
   CH_TRY(P.F ? refresh_numeric(P, std::max(P.batch, 1), s) : alloc_numeric(P, std::max(P.batch, 1), s));
-  if (!P.side) {   // PGO_SIDE_PRIORITY=1: the plain Schur tiles' stream at the lowest dispatch
-                   // priority (measured on C3: 22.0 vs 26.0 it/s -- the starved tiles hold
-                   // the level ends back more than the panel chain gains -- so off)
-    int least = 0, greatest = 0;
-    const char* pr = getenv("PGO_SIDE_PRIORITY");
-    // PGO_SIDE_CUMASK=r (A/B): the plain Schur tiles' stream kept off r of every
-    // 32 CUs (PGO_SIDE_CUMASK_MODE=1: off CUs i with (i / 8) % 32 < r), so the
-    // panel chain's workgroups always find CUs free of them.  Measured on C3:
-    // 13.8 / 20.3 ms against 8.5 / 17.0 ms replays at 1 / 3 lanes
-    // (profiles/r04j_ab_queues_cumask_lookahead.txt), so off
-    const int cum = getenv("PGO_SIDE_CUMASK") ? atoi(getenv("PGO_SIDE_CUMASK")) : 0;
-    if (cum > 0) {
-      const int mode = getenv("PGO_SIDE_CUMASK_MODE") ? atoi(getenv("PGO_SIDE_CUMASK_MODE")) : 0;
-      int dev = 0, ncu = 0;
-      CH_TRY(hipGetDevice(&dev));
-      CH_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-      std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-      for (int i = 0; i < ncu; i++) {
-        const bool off_cu = mode == 1 ? (i / 8) % 32 < cum : i % 32 < cum;
-        if (!off_cu) mask[i / 32] |= 1u << (i % 32);
-      }
-      CH_TRY(hipExtStreamCreateWithCUMask(&P.side, (uint32_t)mask.size(), mask.data()));
-    } else if (pr && pr[0] == '1' && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-      CH_TRY(hipStreamCreateWithPriority(&P.side, hipStreamNonBlocking, least));
-    else
-      CH_TRY(hipStreamCreateWithFlags(&P.side, hipStreamNonBlocking));
+  if (!P.side) {
+    CH_TRY(hipStreamCreateWithFlags(&P.side, hipStreamNonBlocking));
     CH_TRY(hipStreamCreateWithFlags(&P.side2, hipStreamNonBlocking));
     CH_TRY(hipStreamCreateWithFlags(&P.side3, hipStreamNonBlocking));
     // the streams of opt-in knobs exist only with their knob (with
     // GPU_MAX_HW_QUEUES=4 every idle stream still takes a slot in the
     // round-robin mapping of streams to hardware queues)
     if (step_split_threshold() > 0) CH_TRY(hipStreamCreateWithFlags(&P.side5, hipStreamNonBlocking));
-    if (knob_on("PGO_WAVE_STREAMS")) {
-      CH_TRY(hipStreamCreateWithFlags(&P.side6, hipStreamNonBlocking));
-      CH_TRY(hipEventCreateWithFlags(&P.ev6, hipEventDisableTiming));
-    }
     // the deferred far updates fill the CUs the panel chain leaves idle: their
     // stream at the lowest dispatch priority (PGO_FAR_PRIORITY=0: default)
+    int least = 0, greatest = 0;
     const char* fp = getenv("PGO_FAR_PRIORITY");
     if (!knob_on("PGO_FAR"))
       ;
@@ -3394,10 +2842,6 @@ hipError_t chol_upload(CholPlan& P, hipStream_t s) {
       CH_TRY(hipStreamCreateWithFlags(&P.side4, hipStreamNonBlocking));
     for (auto& e : P.evs) CH_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (auto& e : P.fev) CH_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // the four-wave small fronts ask for up to 256 x 33 doubles of LDS (> 64 KiB;
-    // 160 KiB per CU on gfx950)
-    (void)hipFuncSetAttribute((const void*)k_front_wave4<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_front_wave4<kWaveW>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
   }
   return hipSuccess;   // (the fronts' zeroing runs on, stream-ordered before any use)
 }
@@ -3415,8 +2859,6 @@ void chol_free(CholPlan& P) {
   if (P.side3) (void)hipStreamDestroy(P.side3);
   if (P.side4) (void)hipStreamDestroy(P.side4);
   if (P.side5) (void)hipStreamDestroy(P.side5);
-  if (P.side6) (void)hipStreamDestroy(P.side6);
-  if (P.ev6) (void)hipEventDestroy(P.ev6);
   P.sched_scratch.p.reset();   // (not touched by the assignment below)
   P = CholPlan();
 }
@@ -3486,15 +2928,247 @@ double level_at_bytes(const CholPlan& P, int L) {
   return lv.at_bytes = bytes;
 }
 
+// chol_factor's environment knobs (read once, at its first call)
+struct FactorKnobs {
+  // PGO_STEP_STAMPS (diagnostics): the top level's k_step launches record
+  // their step stamps (g_stamps, chol_step_stamps)
+  const bool stamps = getenv("PGO_STEP_STAMPS") != nullptr;
+  // PGO_ABLATE (diagnostics only -- the factor is wrong): skip the named launch
+  // families (small, plain, assemble, vec, first, step) to time what the rest of
+  // the schedule costs in graph mode
+  const char* const ablate = getenv("PGO_ABLATE");
+  bool off(const char* fam) const { return ablate && strstr(ablate, fam); }
+  // (PGO_VEC_FUSE=0, A/B: the frontal vectors in their own launch on the
+  // second side stream, as before round 5)
+  const bool vec_fuse = !(getenv("PGO_VEC_FUSE") && atoi(getenv("PGO_VEC_FUSE")) == 0);
+  // PGO_DEBUG_BAD_PIVOT=r:k (tests): rank r's first k factorisations report a
+  // non-positive pivot that only it has seen -- the partitioned solve must
+  // still take the same decision on every rank
+  const char* const bad_pivot = getenv("PGO_DEBUG_BAD_PIVOT");
+};
+
+// chol_factor, level li: the tile assembly of its fronts and their frontal vectors
+static hipError_t factor_level_assembly(const CholPlan& P, const CholDev& c, const FactorKnobs& kn, size_t li,
+                                        const double* D, const double* V, hipStream_t s, LaunchProfile* prof,
+                                        int nb) {
+  const CholLevel& lv = P.levels[li];
+  const dim3 B256(256);
+  // frontal vectors (fv) in the tile assembly's launch; unfused, on the second
+  // side stream beside the tile assembly (F): disjoint data, both need only
+  // the previous levels; joined before the level's first factor launch
+  const bool vec = !kn.off("vec") && !kn.vec_fuse;
+  const int nvec = !kn.off("vec") && kn.vec_fuse ? lv.front_cnt : 0;
+  if (vec) {
+    CH_TRY(hipEventRecord(P.evs[P.kEvForkMain], s));
+    CH_TRY(hipStreamWaitEvent(P.side2, P.evs[P.kEvForkMain], 0));
+    launch(prof, kFamVecAssemble, [&] { return make_double2(0, lv.vec_bytes * nb); }, k_vec_assemble, dim3(lv.front_cnt, nb), B256,
+           (size_t)lv.maxm * sizeof(double), P.side2, c, (const int*)(P.d_level_fronts + lv.front_off));
+    CH_TRY(hipEventRecord(P.evs[P.kEvJoinSide2], P.side2));
+  }
+  const int ntile = lv.ea_cnt[0] && !kn.off("assemble") ? lv.ea_cnt[0] : 0;
+  if (ntile + nvec > 0)   // (the tile tasks' arrays are read only by workgroups < ntile)
+    launch(prof, kFamAssemble,
+           [&] { return make_double2(0, (level_at_bytes(P, (int)li) * (ntile > 0) + lv.vec_bytes * (nvec > 0)) * nb); },
+           k_assemble_tile, dim3(ntile + nvec, nb), B256, 0, s, c,
+           (const int4*)(P.d_ea_tasks + lv.ea_off[0]), (const int2*)(P.d_at_iptr + lv.ea_off[0]),
+           (const int*)P.d_at_items, (const int4*)P.d_ea_pairs, V, D,
+           (const double*)P.d_lambda, ntile, (const int*)(P.d_level_fronts + lv.front_off));
+  if (vec) CH_TRY(hipStreamWaitEvent(s, P.evs[P.kEvJoinSide2], 0));
+  return hipSuccess;
+}
+
+// chol_factor, level lv: its small fronts (one wavefront / workgroup each).
+// fork_small / fork_wave: side2 / side3 were forked from the main stream and
+// are to be joined at the level's end
+static hipError_t factor_level_small(const CholPlan& P, const CholDev& c, const FactorKnobs& kn, const CholLevel& lv,
+                                     hipStream_t s, LaunchProfile* prof, int nb, bool& fork_small, bool& fork_wave) {
+  const dim3 B256(256);
+  // small fronts on the second side stream, beside the blocked path of the
+  // same level (disjoint fronts); joined before the next level
+  // (the two wavefront classes -- m <= 64, m > 64 -- on two side streams,
+  // concurrently: each is a grid of independent latency-bound waves)
+  fork_small = !lv.small.empty() && !lv.panels.empty();
+  bool lo = false, hi = false;   // wavefront classes with m <= 64 / m > 64
+  for (const SmallClass& sc : lv.small)
+    if (sc.wave) (sc.mmax > 64 ? hi : lo) = true;
+  fork_wave = lo && hi;
+  hipStream_t ss = s;
+  if (fork_small || fork_wave) {
+    CH_TRY(hipEventRecord(P.evs[P.kEvForkMain], s));
+    CH_TRY(hipStreamWaitEvent(P.side2, P.evs[P.kEvForkMain], 0));
+    if (fork_wave) CH_TRY(hipStreamWaitEvent(P.side3, P.evs[P.kEvForkMain], 0));
+    ss = P.side2;
+  }
+  // the wavefront classes' kernels by (m <= 64 | m > 64) x panel width W in
+  // {8, 16, kWaveW}.  m > 64 with W = 32: two waves per front, 15-24 % faster
+  // per 4096 fronts than one wave holding two rows per lane
+  // (profiles/r04e_front_wave_ubench.txt), bitwise the same fronts.  W = 16
+  // stays one wave of per-pivot steps: 102 us against 124 for the two-wave
+  // blocked form on m = 90, w = 12
+  struct WaveKernel {
+    void (*kern)(CholDev, const int*);
+    unsigned block;
+  };
+  static const WaveKernel wave_kernel[2][3] = {
+      {{k_front_wave<8, false>, 64}, {k_front_wave<16, false>, 64}, {k_front_wave<kWaveW, false>, 64}},
+      {{k_front_wave<8, true>, 64}, {k_front_wave<16, true>, 64}, {k_front_wave2<kWaveW>, 128}}};
+  for (const SmallClass& sc : lv.small) {
+    if (kn.off("small")) break;
+    auto small_cost = [&] { return make_double2(sc.flops * nb, 0); };
+    const int* list = P.d_small + sc.off;
+    if (sc.wave) {
+      // the m > 64 classes on the third stream
+      const hipStream_t st = fork_wave && sc.mmax > 64 ? P.side3 : ss;
+      const size_t lds = (size_t)(sc.mmax * (sc.wave + 1) + 130 + sc.wave) * sizeof(double);
+      const WaveKernel& wk = wave_kernel[sc.mmax > 64][sc.wave == 8 ? 0 : sc.wave == 16 ? 1 : 2];
+      launch(prof, kFamFrontWave, small_cost, wk.kern, dim3(sc.cnt, nb), dim3(wk.block), lds, st, c, list);
+    } else {
+      launch(prof, kFamFrontSmall, small_cost, k_front_small, dim3(sc.cnt, nb), B256,
+             (size_t)(sc.mmax * sc.mmax + 64 + sc.mmax) * sizeof(double), ss, c, list);
+    }
+  }
+  return hipSuccess;
+}
+
+// chol_factor, level li: the panel steps of its blocked fronts, the apart plain
+// tiles and the far pieces joined at its end.  xpanels(xi): the distributed
+// top's panel exchange xi (chol_factor)
+template <class XPanels>
+static hipError_t factor_level_panels(const CholPlan& P, const CholDev& c, const FactorKnobs& kn, size_t li,
+                                      hipStream_t s, LaunchProfile* prof, int nb, const XPanels& xpanels) {
+  const CholLevel& lv = P.levels[li];
+  const dim3 B256(256);
+  // apart plain tiles run on P.side (in order, so two of them never touch a
+  // tile at once); plain(j) is joined before step j + plain_lag (1, or 2 when
+  // the look-ahead skip left the next step independent of it), and at the
+  // level's end.  Ring of two join events (P.ev_plain).
+  bool side_pending = false;
+  std::vector<char> on_side(lv.panels.size(), 0);   // plain(j) went to P.side and recorded its event
+  // deferred far updates on P.side4: (join step, event slot) of the pending ones
+  std::vector<int2> far_pending;
+  int fslot = 0;
+  auto join_far = [&](int step) -> hipError_t {   // step -1: all of them
+    for (size_t q = 0; q < far_pending.size();) {
+      if (step < 0 || far_pending[q].x == step) {
+        CH_TRY(hipStreamWaitEvent(s, P.fev[far_pending[q].y], 0));
+        far_pending.erase(far_pending.begin() + q);
+      } else {
+        q++;
+      }
+    }
+    return hipSuccess;
+  };
+  for (size_t j = 0; j < lv.panels.size(); j++) {
+    const PanelStep& ps = lv.panels[j];
+    CH_TRY(join_far((int)j));
+    for (size_t back = 1; back <= 2 && back <= j; back++) {
+      const PanelStep& pp = lv.panels[j - back];
+      if (on_side[j - back] && pp.plain_lag == (int)back)
+        CH_TRY(hipStreamWaitEvent(s, P.evs[P.ev_plain(j - back)], 0));
+    }
+    if (prof) prof->cur_tag = ((int)li << 16) | (ps.kb / kNB + 1);
+    const int4* cols = (const int4*)(P.d_col + ps.col_off);
+    // many first panels (x lanes): diagonal tiles, then the tiles below in a
+    // second launch of higher occupancy; few: one launch with in-launch
+    // hand-offs (kFirstSplit: the fronts x lanes from which to split)
+    if (ps.potrf_cnt && !kn.off("first")) {
+      if (ps.potrf_cnt * nb >= kFirstSplit && ps.fcol_cnt > 0) {
+        launch(prof, kFamPanelFirst, [&] { return make_double2(ps.first_flops * nb, 0); }, k_first_diag,
+               dim3(ps.potrf_cnt, nb), B256, 0, s, c, (const int*)(P.d_potrf + ps.potrf_off));
+        launch(prof, kFamPanelFirst, [&] { return make_double2(0, 0); }, k_first_trsm, dim3(ps.fcol_cnt, nb), B256,
+               0, s, c, cols);
+      } else {
+        launch(prof, kFamPanelFirst, [&] { return make_double2(ps.first_flops * nb, 0); }, k_panel_first,
+               dim3(ps.potrf_cnt + ps.fcol_cnt, nb), B256, 0, s, c, (const int*)(P.d_potrf + ps.potrf_off),
+               ps.potrf_cnt, cols);
+      }
+    }
+    CH_TRY(xpanels(ps.xfirst));
+    const int4* tiles = (const int4*)(P.d_syrk + ps.syrk_off);
+    const int nin = ps.syrk_inline && !kn.off("plain") ? ps.syrk_cnt : 0;
+    const bool apart = ps.syrk_cnt > 0 && !ps.syrk_inline && !kn.off("plain");   // plain tiles in their own launch
+    const bool step = ps.sdiag_cnt + ps.col_cnt + ps.prep_cnt + nin > 0 && !kn.off("step");
+    auto plain = [&](hipStream_t st, int first, int cnt, double flops) {
+      const bool big = ps.syrk_tile == kBigTile;
+      launch(prof, big ? kFamPanelSyrk128 : kFamPanelSyrk, [&] { return make_double2(flops * nb, 0); },
+             big ? k_panel_syrk128 : k_panel_syrk_lds, dim3(cnt, nb), B256, 0, st, c, tiles + first, ps.kb);
+    };
+    if (apart) {   // on the side stream (beside k_step, behind the earlier plains)
+      CH_TRY(hipEventRecord(P.evs[P.kEvForkPlain], s));
+      CH_TRY(hipStreamWaitEvent(P.side, P.evs[P.kEvForkPlain], 0));
+    }
+    // many diagonal tiles (x lanes): the step as three launches -- the
+    // diagonal tiles (k_step_diag: 2 workgroups per CU) beside the column
+    // block's, prep and inline tile updates (k_panel_syrk_lds on P.side5:
+    // 4 per CU), then the column block's solves (k_first_trsm) -- instead of
+    // one k_step whose column workgroups hold a diagonal workgroup's LDS and
+    // registers while they wait; same arithmetic (the tile kernels compute a
+    // tile's elements alike), bitwise k_step's factor
+    const int step_split = step_split_threshold();
+    const bool split = step && step_split > 0 && ps.sdiag_cnt * nb >= step_split && ps.col_cnt > 0;
+    if (split) {
+      const int4* cupd = cols + ps.fcol_cnt;   // col then prep tasks: 64x64 tile updates
+      CH_TRY(hipEventRecord(P.evs[P.kEvForkMain], s));
+      CH_TRY(hipStreamWaitEvent(P.side5, P.evs[P.kEvForkMain], 0));
+      launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.colupd_flops * nb, 0); }, k_panel_syrk_lds,
+             dim3(ps.col_cnt + ps.prep_cnt, nb), B256, 0, P.side5, c, cupd, ps.kb);
+      if (nin)
+        launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.plain_flops * nb, 0); }, k_panel_syrk_lds,
+               dim3(nin, nb), B256, 0, P.side5, c, tiles, ps.kb);
+      CH_TRY(hipEventRecord(P.evs[P.kEvJoinSide2], P.side5));
+      launch(prof, kFamStepDiag, [&] { return make_double2(ps.diag_flops * nb, 0); }, k_step_diag,
+             dim3(ps.sdiag_cnt, nb), B256, 0, s, c, (const int4*)(P.d_sdiag + ps.sdiag_off), ps.kb);
+      CH_TRY(hipStreamWaitEvent(s, P.evs[P.kEvJoinSide2], 0));
+      launch(prof, kFamColTrsm, [&] { return make_double2(ps.trsm_flops * nb, 0); }, k_first_trsm,
+             dim3(ps.col_cnt, nb), B256, 0, s, c, cupd);
+    } else if (step)
+      launch(prof, kFamStep, [&] { return make_double2(ps.step_flops * nb, 0); }, k_step,
+             dim3(ps.sdiag_cnt + ps.col_cnt + ps.prep_cnt + nin, nb), B256, 0, s, c,
+             (const int4*)(P.d_sdiag + ps.sdiag_off), ps.sdiag_cnt, cols + ps.fcol_cnt, ps.col_cnt, ps.prep_cnt,
+             tiles, ps.kb,
+             kn.stamps && li + 1 == P.levels.size() && ps.kb / kNB < kMaxStampSlots ? ps.kb / kNB : -1);
+    if (apart) {   // (never on the main stream: an earlier plain may still run on P.side)
+      const int nnear = ps.syrk_cnt - ps.far_cnt;
+      plain(P.side, 0, nnear, ps.plain_flops - ps.far_flops);
+      CH_TRY(hipEventRecord(P.evs[P.ev_plain(j)], P.side));
+      side_pending = true;
+      on_side[j] = 1;
+      if (ps.far_cnt > 0) {   // the far pieces: on P.side4 (behind the earlier far launches), each joined late
+        CH_TRY(hipStreamWaitEvent(P.side4, P.evs[P.kEvForkPlain], 0));
+        for (int q = ps.far_p0; q < ps.far_p0 + ps.far_np; q++) {
+          const int4 fp = lv.far_pieces[q];
+          if (fp.z == 0) continue;
+          int busy = -2;   // (a ring slot still pending: joined now)
+          for (const int2& pend : far_pending)
+            if (pend.y == fslot) busy = pend.x;
+          if (busy != -2) CH_TRY(join_far(busy));
+          plain(P.side4, fp.y, fp.z, lv.far_piece_flops[q]);
+          CH_TRY(hipEventRecord(P.fev[fslot], P.side4));
+          far_pending.push_back(make_int2(fp.w, fslot));
+          fslot = (fslot + 1) % 8;
+        }
+      }
+    }
+    // the panel this step factored, to every rank (the apart plain tiles
+    // beside it neither read nor write its columns)
+    CH_TRY(xpanels(ps.xstep));
+  }
+  if (side_pending) {   // every apart plain of the level done before the next level
+    CH_TRY(hipEventRecord(P.evs[P.kEvForkPlain], P.side));
+    CH_TRY(hipStreamWaitEvent(s, P.evs[P.kEvForkPlain], 0));
+  }
+  CH_TRY(join_far(-1));
+  return hipSuccess;
+}
+
 hipError_t chol_factor(const CholPlan& P, const double* D, const double* V, const double* b, double scale_b,
                        hipStream_t s, LaunchProfile* prof, int nb, ExchangeHook* hook) {
   if (P.n == 0) return hipSuccess;
   if (nb < 1 || nb > P.batch) return hipErrorInvalidValue;
+  static const FactorKnobs kn;
   const CholDev c = dev_view(P);
-  const dim3 B256(256);
-  static const bool stamps = getenv("PGO_STEP_STAMPS") != nullptr;
   launch(prof, kFamPerm, [&] { return make_double2(0, 48.0 * P.n * nb); }, k_perm_in, dim3((P.n + 255) / 256, nb),
-         B256, 0, s, c, b, scale_b, P.n);
+         dim3(256), 0, s, c, b, scale_b, P.n);
   CH_TRY(hipMemsetAsync(P.d_flag, 0, sizeof(int) * nb, s));
   CH_TRY(hipMemsetAsync(P.d_stepflag, 0, sizeof(int) * std::max(P.ns, 1) * nb, s));
   const bool part = P.part_size > 1;
@@ -3533,246 +3207,26 @@ hipError_t chol_factor(const CholPlan& P, const double* D, const double* V, cons
                                                     P.part_rank);
     return hipGetLastError();
   };
-  // PGO_ABLATE (diagnostics only -- the factor is wrong): skip the named launch
-  // families (small, plain, assemble, vec, first, step) to time what the rest of
-  // the schedule costs in graph mode
-  static const char* ablate = getenv("PGO_ABLATE");
-  auto off = [&](const char* fam) { return ablate && strstr(ablate, fam); };
   for (size_t li = 0; li < P.levels.size(); li++) {
     const CholLevel& lv = P.levels[li];
     if (prof) prof->cur_tag = (int)li << 16;
     if (part && (int)li == P.split) CH_TRY(exchange());
-    // frontal vectors (fv) on the second side stream beside the tile assembly
-    // (F): disjoint data, both need only the previous levels; joined before the
-    // level's first factor launch
-    static const bool asm_push = getenv("PGO_ASM_PUSH") && atoi(getenv("PGO_ASM_PUSH")) == 1;
-    // (PGO_VEC_FUSE=0, A/B: the frontal vectors in their own launch on the
-    // second side stream, as before round 5)
-    static const bool vec_fuse = !(getenv("PGO_VEC_FUSE") && atoi(getenv("PGO_VEC_FUSE")) == 0) && !asm_push;
-    const bool vec = !off("vec") && !vec_fuse;
-    const int nvec = !off("vec") && vec_fuse ? lv.front_cnt : 0;
-    if (vec) {
-      CH_TRY(hipEventRecord(P.evs[0], s));
-      CH_TRY(hipStreamWaitEvent(P.side2, P.evs[0], 0));
-      launch(prof, kFamVecAssemble, [&] { return make_double2(0, lv.vec_bytes * nb); }, k_vec_assemble, dim3(lv.front_cnt, nb), B256,
-             (size_t)lv.maxm * sizeof(double), P.side2, c, (const int*)(P.d_level_fronts + lv.front_off));
-      CH_TRY(hipEventRecord(P.evs[1], P.side2));
-    }
-    // (PGO_ASM_UNROLL: children whose loads are in flight together, 1 or 2)
-    static const int asm_unroll = getenv("PGO_ASM_UNROLL") ? atoi(getenv("PGO_ASM_UNROLL")) : 1;
-    const int ntile = lv.ea_cnt[0] && !off("assemble") ? lv.ea_cnt[0] : 0;
-    if (asm_push && ntile)
-      launch(prof, kFamAssemble, [&] { return make_double2(0, level_at_bytes(P, (int)li) * nb); },
-             k_assemble_tile_push, dim3(ntile, nb), B256, 0, s, c,
-             (const int4*)(P.d_ea_tasks + lv.ea_off[0]), (const int2*)(P.d_at_iptr + lv.ea_off[0]),
-             (const int*)P.d_at_items, (const int4*)P.d_ea_pairs, V, D,
-             (const double*)P.d_lambda);
-    else if (ntile + nvec > 0)   // (the tile tasks' arrays are read only by workgroups < ntile)
-      launch(prof, kFamAssemble,
-             [&] { return make_double2(0, (level_at_bytes(P, (int)li) * (ntile > 0) + lv.vec_bytes * (nvec > 0)) * nb); },
-             asm_unroll == 2 ? k_assemble_tile<2> : k_assemble_tile<1>, dim3(ntile + nvec, nb), B256, 0, s, c,
-             (const int4*)(P.d_ea_tasks + lv.ea_off[0]), (const int2*)(P.d_at_iptr + lv.ea_off[0]),
-             (const int*)P.d_at_items, (const int4*)P.d_ea_pairs, V, D,
-             (const double*)P.d_lambda, ntile, (const int*)(P.d_level_fronts + lv.front_off));
-    if (vec) CH_TRY(hipStreamWaitEvent(s, P.evs[1], 0));
-    // small fronts on the second side stream, beside the blocked path of the
-    // same level (disjoint fronts); joined before the next level
-    // (the two wavefront classes -- m <= 64, m > 64 -- on two side streams,
-    // concurrently: each is a grid of independent latency-bound waves)
-    const bool fork_small = !lv.small.empty() && !lv.panels.empty();
-    bool lo = false, hi = false;   // wavefront classes with m <= 64 / m > 64
-    for (const SmallClass& sc : lv.small)
-      if (sc.wave) (sc.mmax > 64 ? hi : lo) = true;
-    const bool fork_wave = lo && hi;
-    // PGO_WAVE_STREAMS=1 (A/B): the m > 64 classes narrower than kWaveW (few
-    // fronts, latency-bound) on a fourth side stream instead of ahead of the
-    // kWaveW class on the third
-    static const bool wave_streams = knob_on("PGO_WAVE_STREAMS");
-    hipStream_t ss = s;
-    if (fork_small || fork_wave) {
-      CH_TRY(hipEventRecord(P.evs[0], s));
-      CH_TRY(hipStreamWaitEvent(P.side2, P.evs[0], 0));
-      if (fork_wave) CH_TRY(hipStreamWaitEvent(P.side3, P.evs[0], 0));
-      if (fork_wave && wave_streams) CH_TRY(hipStreamWaitEvent(P.side6, P.evs[0], 0));
-      ss = P.side2;
-    }
-    for (const SmallClass& sc : lv.small) {
-      if (off("small")) break;
-      auto small_cost = [&] { return make_double2(sc.flops * nb, 0); };
-      const int* list = P.d_small + sc.off;
-      if (sc.wave) {
-        // classes by (m <= 64 | m > 64) x panel width W in {8, 16, 32}; the
-        // m > 64 ones on the third stream
-        const hipStream_t st = fork_wave && sc.mmax > 64 ? (wave_streams && sc.wave < kWaveW ? P.side6 : P.side3) : ss;
-        const size_t lds = (size_t)(sc.mmax * (sc.wave + 1) + 130 + sc.wave) * sizeof(double);
-        const dim3 g(sc.cnt, nb), b(64);
-        // (m > 64 with W = 32: two waves per front, k_front_wave2, 15-24 % faster
-        // per 4096 fronts (profiles/r04e_front_wave_ubench.txt); PGO_WAVE2=0: one
-        // wave holding two rows per lane -- bitwise the same fronts.  W = 16
-        // stays one wave of per-pivot steps: 102 us against 124 for the two-wave
-        // blocked form on m = 90, w = 12; PGO_WAVE2=2 forces the two waves there)
-        static const int wave2_mode = getenv("PGO_WAVE2") ? atoi(getenv("PGO_WAVE2")) : 1;
-        const bool wave2 = wave2_mode != 0;
-        const dim3 b2(128);
-        if (sc.mmax > kSmallFront) {   // 128 < m <= 256: four waves (k_front_wave4), W 16 or 32
-          if (sc.wave == 16) launch(prof, kFamFrontWave, small_cost, k_front_wave4<16>, g, dim3(256), lds, st, c, list);
-          else launch(prof, kFamFrontWave, small_cost, k_front_wave4<kWaveW>, g, dim3(256), lds, st, c, list);
-        } else if (sc.mmax > 64) {
-          if (sc.wave == 8) launch(prof, kFamFrontWave, small_cost, k_front_wave<8, true>, g, b, lds, st, c, list);
-          else if (sc.wave == 16 && wave2_mode == 2) launch(prof, kFamFrontWave, small_cost, k_front_wave2<16>, g, b2, lds, st, c, list);
-          else if (sc.wave == 16) launch(prof, kFamFrontWave, small_cost, k_front_wave<16, true>, g, b, lds, st, c, list);
-          else if (wave2) launch(prof, kFamFrontWave, small_cost, k_front_wave2<kWaveW>, g, b2, lds, st, c, list);
-          else launch(prof, kFamFrontWave, small_cost, k_front_wave<kWaveW, true>, g, b, lds, st, c, list);
-        } else {
-          if (sc.wave == 8) launch(prof, kFamFrontWave, small_cost, k_front_wave<8, false>, g, b, lds, st, c, list);
-          else if (sc.wave == 16) launch(prof, kFamFrontWave, small_cost, k_front_wave<16, false>, g, b, lds, st, c, list);
-          else launch(prof, kFamFrontWave, small_cost, k_front_wave<kWaveW, false>, g, b, lds, st, c, list);
-        }
-      } else {
-        launch(prof, kFamFrontSmall, small_cost, k_front_small, dim3(sc.cnt, nb), B256,
-               (size_t)(sc.mmax * sc.mmax + 64 + sc.mmax) * sizeof(double), ss, c, list);
-      }
-    }
-    // apart plain tiles run on P.side (in order, so two of them never touch a
-    // tile at once); plain(j) is joined before step j + plain_lag (1, or 2 when
-    // the look-ahead skip left the next step independent of it), and at the
-    // level's end.  Ring of two join events (evs[3], evs[5]).
-    bool side_pending = false;
-    std::vector<char> on_side(lv.panels.size(), 0);   // plain(j) went to P.side and recorded its event
-    // deferred far updates on P.side4: (join step, event slot) of the pending ones
-    std::vector<int2> far_pending;
-    int fslot = 0;
-    auto join_far = [&](int step) -> hipError_t {   // step -1: all of them
-      for (size_t q = 0; q < far_pending.size();) {
-        if (step < 0 || far_pending[q].x == step) {
-          CH_TRY(hipStreamWaitEvent(s, P.fev[far_pending[q].y], 0));
-          far_pending.erase(far_pending.begin() + q);
-        } else {
-          q++;
-        }
-      }
-      return hipSuccess;
-    };
-    for (size_t j = 0; j < lv.panels.size(); j++) {
-      const PanelStep& ps = lv.panels[j];
-      CH_TRY(join_far((int)j));
-      for (size_t back = 1; back <= 2 && back <= j; back++) {
-        const PanelStep& pp = lv.panels[j - back];
-        if (on_side[j - back] && pp.plain_lag == (int)back)
-          CH_TRY(hipStreamWaitEvent(s, P.evs[(j - back) & 1 ? 5 : 3], 0));
-      }
-      if (prof) prof->cur_tag = ((int)li << 16) | (ps.kb / kNB + 1);
-      const int4* cols = (const int4*)(P.d_col + ps.col_off);
-      // many first panels (x lanes): diagonal tiles, then the tiles below in a
-      // second launch of higher occupancy; few: one launch with in-launch
-      // hand-offs (PGO_FIRST_SPLIT: the fronts x lanes from which to split)
-      static const int first_split = getenv("PGO_FIRST_SPLIT") ? atoi(getenv("PGO_FIRST_SPLIT")) : 64;
-      if (ps.potrf_cnt && !off("first")) {
-        if (ps.potrf_cnt * nb >= first_split && ps.fcol_cnt > 0) {
-          launch(prof, kFamPanelFirst, [&] { return make_double2(ps.first_flops * nb, 0); }, k_first_diag,
-                 dim3(ps.potrf_cnt, nb), B256, 0, s, c, (const int*)(P.d_potrf + ps.potrf_off));
-          launch(prof, kFamPanelFirst, [&] { return make_double2(0, 0); }, k_first_trsm, dim3(ps.fcol_cnt, nb), B256,
-                 0, s, c, cols);
-        } else {
-          launch(prof, kFamPanelFirst, [&] { return make_double2(ps.first_flops * nb, 0); }, k_panel_first,
-                 dim3(ps.potrf_cnt + ps.fcol_cnt, nb), B256, 0, s, c, (const int*)(P.d_potrf + ps.potrf_off),
-                 ps.potrf_cnt, cols);
-        }
-      }
-      CH_TRY(xpanels(ps.xfirst));
-      const int4* tiles = (const int4*)(P.d_syrk + ps.syrk_off);
-      const int nin = ps.syrk_inline && !off("plain") ? ps.syrk_cnt : 0;
-      const bool apart = ps.syrk_cnt > 0 && !ps.syrk_inline && !off("plain");   // plain tiles in their own launch
-      const bool step = ps.sdiag_cnt + ps.col_cnt + ps.prep_cnt + nin > 0 && !off("step");
-      auto plain = [&](hipStream_t st, int first, int cnt, double flops) {
-        const bool big = ps.syrk_tile == kBigTile;
-        launch(prof, big ? kFamPanelSyrk128 : kFamPanelSyrk, [&] { return make_double2(flops * nb, 0); },
-               big ? k_panel_syrk128 : k_panel_syrk_lds, dim3(cnt, nb), B256, 0, st, c, tiles + first, ps.kb);
-      };
-      if (apart) {   // on the side stream (beside k_step, behind the earlier plains)
-        CH_TRY(hipEventRecord(P.evs[2], s));
-        CH_TRY(hipStreamWaitEvent(P.side, P.evs[2], 0));
-      }
-      // many diagonal tiles (x lanes): the step as three launches -- the
-      // diagonal tiles (k_step_diag: 2 workgroups per CU) beside the column
-      // block's, prep and inline tile updates (k_panel_syrk_lds on P.side5:
-      // 4 per CU), then the column block's solves (k_first_trsm) -- instead of
-      // one k_step whose column workgroups hold a diagonal workgroup's LDS and
-      // registers while they wait; same arithmetic (the tile kernels compute a
-      // tile's elements alike), bitwise k_step's factor
-      const int step_split = step_split_threshold();
-      const bool split = step && step_split > 0 && ps.sdiag_cnt * nb >= step_split && ps.col_cnt > 0;
-      if (split) {
-        const int4* cupd = cols + ps.fcol_cnt;   // col then prep tasks: 64x64 tile updates
-        CH_TRY(hipEventRecord(P.evs[0], s));
-        CH_TRY(hipStreamWaitEvent(P.side5, P.evs[0], 0));
-        launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.colupd_flops * nb, 0); }, k_panel_syrk_lds,
-               dim3(ps.col_cnt + ps.prep_cnt, nb), B256, 0, P.side5, c, cupd, ps.kb);
-        if (nin)
-          launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.plain_flops * nb, 0); }, k_panel_syrk_lds,
-                 dim3(nin, nb), B256, 0, P.side5, c, tiles, ps.kb);
-        CH_TRY(hipEventRecord(P.evs[1], P.side5));
-        launch(prof, kFamStepDiag, [&] { return make_double2(ps.diag_flops * nb, 0); }, k_step_diag,
-               dim3(ps.sdiag_cnt, nb), B256, 0, s, c, (const int4*)(P.d_sdiag + ps.sdiag_off), ps.kb);
-        CH_TRY(hipStreamWaitEvent(s, P.evs[1], 0));
-        launch(prof, kFamColTrsm, [&] { return make_double2(ps.trsm_flops * nb, 0); }, k_first_trsm,
-               dim3(ps.col_cnt, nb), B256, 0, s, c, cupd);
-      } else if (step)
-        launch(prof, kFamStep, [&] { return make_double2(ps.step_flops * nb, 0); }, k_step,
-               dim3(ps.sdiag_cnt + ps.col_cnt + ps.prep_cnt + nin, nb), B256, 0, s, c,
-               (const int4*)(P.d_sdiag + ps.sdiag_off), ps.sdiag_cnt, cols + ps.fcol_cnt, ps.col_cnt, ps.prep_cnt,
-               tiles, ps.kb,
-               stamps && li + 1 == P.levels.size() && ps.kb / kNB < kMaxStampSlots ? ps.kb / kNB : -1);
-      if (apart) {   // (never on the main stream: an earlier plain may still run on P.side)
-        const int nnear = ps.syrk_cnt - ps.far_cnt;
-        plain(P.side, 0, nnear, ps.plain_flops - ps.far_flops);
-        CH_TRY(hipEventRecord(P.evs[j & 1 ? 5 : 3], P.side));
-        side_pending = true;
-        on_side[j] = 1;
-        if (ps.far_cnt > 0) {   // the far pieces: on P.side4 (behind the earlier far launches), each joined late
-          CH_TRY(hipStreamWaitEvent(P.side4, P.evs[2], 0));
-          for (int q = ps.far_p0; q < ps.far_p0 + ps.far_np; q++) {
-            const int4 fp = lv.far_pieces[q];
-            if (fp.z == 0) continue;
-            int busy = -2;   // (a ring slot still pending: joined now)
-            for (const int2& pend : far_pending)
-              if (pend.y == fslot) busy = pend.x;
-            if (busy != -2) CH_TRY(join_far(busy));
-            plain(P.side4, fp.y, fp.z, lv.far_piece_flops[q]);
-            CH_TRY(hipEventRecord(P.fev[fslot], P.side4));
-            far_pending.push_back(make_int2(fp.w, fslot));
-            fslot = (fslot + 1) % 8;
-          }
-        }
-      }
-      // the panel this step factored, to every rank (the apart plain tiles
-      // beside it neither read nor write its columns)
-      CH_TRY(xpanels(ps.xstep));
-    }
-    if (side_pending) {   // every apart plain of the level done before the next level
-      CH_TRY(hipEventRecord(P.evs[2], P.side));
-      CH_TRY(hipStreamWaitEvent(s, P.evs[2], 0));
-    }
-    CH_TRY(join_far(-1));
-    if (fork_small || fork_wave) {
-      CH_TRY(hipEventRecord(P.evs[1], P.side2));
-      CH_TRY(hipStreamWaitEvent(s, P.evs[1], 0));
+    bool fork_small = false, fork_wave = false;
+    CH_TRY(factor_level_assembly(P, c, kn, li, D, V, s, prof, nb));
+    CH_TRY(factor_level_small(P, c, kn, lv, s, prof, nb, fork_small, fork_wave));
+    CH_TRY(factor_level_panels(P, c, kn, li, s, prof, nb, xpanels));
+    if (fork_small || fork_wave) {   // the small fronts done before the next level
+      CH_TRY(hipEventRecord(P.evs[P.kEvJoinSide2], P.side2));
+      CH_TRY(hipStreamWaitEvent(s, P.evs[P.kEvJoinSide2], 0));
       if (fork_wave) {
-        CH_TRY(hipEventRecord(P.evs[4], P.side3));
-        CH_TRY(hipStreamWaitEvent(s, P.evs[4], 0));
-        if (wave_streams) {
-          CH_TRY(hipEventRecord(P.ev6, P.side6));
-          CH_TRY(hipStreamWaitEvent(s, P.ev6, 0));
-        }
+        CH_TRY(hipEventRecord(P.evs[P.kEvJoinSide3], P.side3));
+        CH_TRY(hipStreamWaitEvent(s, P.evs[P.kEvJoinSide3], 0));
       }
     }
     CH_TRY(xpanels(lv.xtail));
   }
   if (part && P.split >= (int)P.levels.size()) CH_TRY(exchange());
-  // PGO_DEBUG_BAD_PIVOT=r:k (tests): rank r's first k factorisations report a
-  // non-positive pivot that only it has seen -- the partitioned solve must
-  // still take the same decision on every rank
-  static const char* bad = getenv("PGO_DEBUG_BAD_PIVOT");
+  const char* bad = kn.bad_pivot;
   static int bad_left = bad && strchr(bad, ':') ? atoi(strchr(bad, ':') + 1) : 0;
   if (bad && bad_left > 0 && atoi(bad) == P.part_rank) {
     bad_left--;

@@ -213,19 +213,6 @@ static double front_flops(int m, int w) {
   return f;
 }
 
-// blocked path (64-column panels) vs one workgroup / wavefront per front
-// Fronts of 128 < m <= 256 rows and w <= kWaveW pivots: one four-wave
-// workgroup each (k_front_wave4) instead of the blocked path, though stored
-// packed -- opt-in, PGO_WAVE4=1: measured on C3 8.86 / 16.75 ms against 8.44 /
-// 16.92 ms replays at 1 / 3 lanes, 44.0 against 44.5 it/s
-// (profiles/r04m_ab_wave4.txt: one workgroup per front is a longer latency
-// than the blocked path's tiles spread over the chip)
-static bool wave4_front(int m, int w) {
-  static const bool on = getenv("PGO_WAVE4") && atoi(getenv("PGO_WAVE4")) == 1;
-  return on && m > kSmallFront && m <= 2 * kSmallFront && w <= kWaveW;
-}
-static bool is_blocked(const CholPlan& P, int s) { return front_packed(P.m[s], P.w[s]) && !wave4_front(P.m[s], P.w[s]); }
-
 // Column owners of the distributed top (see chol_analyze): per top front s
 // (owner[s] < 0) its m columns at cown[off[s] ..]: rank, or -1 (every rank).
 static void column_owners(const CholPlan& P, const std::vector<int>& owner, int psz, std::vector<int>& off,
@@ -240,7 +227,7 @@ static void column_owners(const CholPlan& P, const std::vector<int>& owner, int 
     off[s] = (int)cown.size();
     cown.resize(cown.size() + m, -1);
     int* own = cown.data() + off[s];
-    const bool blk = is_blocked(P, s);
+    const bool blk = front_packed(m, w);   // the blocked path (64-column panels)
     const int wr = blk ? std::min(m, (w + kNB - 1) / kNB * kNB) : 0;
     for (int col = 0; col < wr; col += kNB, rr++)
       for (int j = col; j < std::min(col + kNB, wr); j++) own[j] = rr % psz;
@@ -511,7 +498,8 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
     bylevel.swap(kept);
     P.split = split;
   }
-  auto blocked = [&](int s) { return is_blocked(P, s); };
+  // blocked path (64-column panels) vs one workgroup / wavefront per front
+  auto blocked = [&](int s) { return front_packed(P.m[s], P.w[s]); };
   // ---- distributed top (part_size > 1): the top fronts' columns are dealt to
   // the ranks instead of every rank factoring every top front.  A blocked top
   // front's pivot columns go by 64-column panel, round robin (continuing over
@@ -734,15 +722,13 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
         while (P.m[s] > classes[q]) q++;
         bucket[q].push_back(s);
       }
-      // m <= 64 (one row per lane) | 64 < m <= 128 | 128 < m <= 256 (four waves)  x  w <= 8 | 16 | 32
-      // (the four-wave class has no W = 8 form: its w <= 8 fronts go with W = 16)
-      for (int cls = 0; cls < 9; cls++) {
+      // m <= 64 (one row per lane) | 64 < m <= 128  x  w <= 8 | 16 | 32
+      for (int cls = 0; cls < 6; cls++) {
         const int rc = cls / 3, W = cls % 3 == 0 ? 8 : cls % 3 == 1 ? 16 : kWaveW;
-        const int Wlo = cls % 3 == 0 ? 0 : (rc == 2 && W == 16 ? 0 : W / 2);
-        if (rc == 2 && W == 8) continue;
+        const int Wlo = cls % 3 == 0 ? 0 : W / 2;
         std::vector<int> part;
         for (int s : wave) {
-          const int mc = P.m[s] <= 64 ? 0 : P.m[s] <= kSmallFront ? 1 : 2;
+          const int mc = P.m[s] <= 64 ? 0 : 1;
           if (mc == rc && P.w[s] > Wlo && P.w[s] <= W) part.push_back(s);
         }
         if (part.empty()) continue;

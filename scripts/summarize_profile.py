@@ -34,7 +34,7 @@ def counters(path):
 
 
 def short(name):
-    """'void pgo::k_panel_syrk<...>(pgo::CholDev, ...)' -> 'k_panel_syrk'."""
+    """'void pgo::k_front_wave<...>(pgo::CholDev, ...)' -> 'k_front_wave'."""
     base = name.split("(")[0].split("<")[0]
     return base.split("::")[-1].split(" ")[-1]
 

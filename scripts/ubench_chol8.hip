@@ -1,5 +1,5 @@
-// Cycles of the lane-redundant 8x8 pieces of the diagonal-block chain
-// (chol8_lane, inv8_lane of pgo_chol.hip) on one wave, back to back with a
+// Cycles of the lane-held 8x8 pieces of the diagonal-block chain
+// (chol8_lane, fwd8_lane of pgo_chol.hip) on one wave, back to back with a
 // data dependence between calls, and of a 16x16 lane-redundant factor +
 // inverse in registers (chol16 / inv16 below: 136 values per lane), to price
 // the diagonal block's alternatives.
@@ -34,7 +34,7 @@ __device__ __forceinline__ bool chol16_lane(double (&a)[136], double (&iv)[16]) 
   return bad;
 }
 
-template <int kMode>   // 0: chol8, 1: chol8 + inv8, 2: chol16, 3: 2x(chol8+inv8) (the diag16 scalar part)
+template <int kMode>   // 0: chol8, 1: chol8 + fwd8, 2: chol16, 3: 2x(chol8+fwd8) (diag16_fs's scalar part)
 __global__ __launch_bounds__(64) void u_chol(const double* A, double* out, long long* clk, int reps) {
   const int l = threadIdx.x;
   double a8[36], iv8[8], a16[136], iv16[16];
@@ -50,16 +50,18 @@ __global__ __launch_bounds__(64) void u_chol(const double* A, double* out, long 
 #pragma unroll
       for (int i = 0; i < 36; i++) b[i] = a8[i] + acc * 1e-300;
       acc += chol8_lane(b, iv8) ? 1.0 : 0.0;
-      if (kMode >= 1) inv8_lane(b, iv8);
+      double x[8];   // one right-hand side per lane (e_l in lanes 0-7)
+#pragma unroll
+      for (int k = 0; k < 8; k++) x[k] = k == l ? 1.0 : 0.0;
+      if (kMode >= 1) fwd8_lane(b, iv8, x);
       if (kMode == 3) {
         double c[36];
 #pragma unroll
-        for (int i = 0; i < 36; i++) c[i] = a8[i] + b[i] * 1e-300;
+        for (int i = 0; i < 36; i++) c[i] = a8[i] + x[7] * 1e-300;
         acc += chol8_lane(c, iv8) ? 1.0 : 0.0;
-        inv8_lane(c, iv8);
-        acc += c[35] * 1e-300;
+        fwd8_lane(c, iv8, x);
       }
-      acc += b[35] * 1e-300;
+      acc += (b[35] + x[7]) * 1e-300;
     } else {
       double b[136];
 #pragma unroll
@@ -99,8 +101,8 @@ int main() {
   hipMemcpy(dA, h, sizeof(h), hipMemcpyHostToDevice);
   hipMemcpy(dA8, h8, sizeof(h8), hipMemcpyHostToDevice);
   run<0>("chol8_lane", dA8, dO, dc);
-  run<1>("chol8_lane + inv8_lane", dA8, dO, dc);
-  run<3>("2 x (chol8 + inv8)", dA8, dO, dc);
+  run<1>("chol8_lane + fwd8_lane", dA8, dO, dc);
+  run<3>("2 x (chol8 + fwd8)", dA8, dO, dc);
   run<2>("chol16_lane", dA, dO, dc);
   return 0;
 }

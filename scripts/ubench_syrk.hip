@@ -1,4 +1,4 @@
-// Microbenchmark of the Schur-update kernels (k_panel_syrk 64x64 tiles,
+// Microbenchmark of the Schur-update kernels (k_panel_syrk_lds 64x64 tiles,
 // k_panel_syrk128 128x128 tiles) on one front: the outer update of depth 256
 // after the first kKB block, the largest launches of a C3 factorisation.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include scripts/ubench_syrk.hip -o graphslam_amd/build/ubench_syrk
@@ -16,7 +16,7 @@ using namespace pgo;
 __global__ __launch_bounds__(256) void k_panel_syrk_lds32(CholDev c, const int4* __restrict__ tasks, int kb) {
   lane_offset(c);
   __shared__ __attribute__((aligned(16))) double smem[4 * 32 * 68];
-  syrk_lds_body<false, 32>(c, tasks[blockIdx.x], kb, smem);
+  syrk_lds_body<32>(c, tasks[blockIdx.x], kb, smem);
 }
 
 __device__ long long g_mclk[4];
@@ -138,8 +138,8 @@ int main(int argc, char** argv) {
   for (const int kb : {192, 0}) {
   const int be = 256, depth = kb + 64;
   const double flops = (double)depth * (M - be) * (M - be + 1.0);
-  for (int T : {64, 65, 66, 67, 128}) {   // 65: the LDS-staged 64x64 kernel; 66: the same with the C tile prefetched; 67: 32-column chunks
-    const int TT = (T >= 65 && T <= 67) ? 64 : T;
+  for (int T : {65, 67, 128}) {   // 65: the LDS-staged 64x64 kernel; 67: the same with 32-column chunks
+    const int TT = T == 128 ? 128 : 64;
     std::vector<int4> tasks;
     for (int c0 = be; c0 < M; c0 += TT)
       for (int r0 = c0; r0 < M; r0 += TT) tasks.push_back(make_int4(0, r0, c0, 0));
@@ -154,9 +154,7 @@ int main(int argc, char** argv) {
     for (int r = 0; r < reps; r++) {
       hipMemcpyAsync(F, F0, n * 8, hipMemcpyDeviceToDevice, st);
       hipEventRecord(a, st);
-      if (T == 64) k_panel_syrk<<<(int)tasks.size(), 256, 0, st>>>(c, dt, kb);
-      else if (T == 65) k_panel_syrk_lds<<<(int)tasks.size(), 256, 0, st>>>(c, dt, kb);
-      else if (T == 66) k_panel_syrk_lds_pc<<<(int)tasks.size(), 256, 0, st>>>(c, dt, kb);
+      if (T == 65) k_panel_syrk_lds<<<(int)tasks.size(), 256, 0, st>>>(c, dt, kb);
       else if (T == 67) k_panel_syrk_lds32<<<(int)tasks.size(), 256, 0, st>>>(c, dt, kb);
       else k_panel_syrk128<<<(int)tasks.size(), 256, 0, st>>>(c, dt, kb);
       hipEventRecord(b, st);
