@@ -173,20 +173,92 @@ int check_assembly(const pgo::CholPlan& P) {
     if (it.y != (int)want.size() || !std::equal(want.begin(), want.end(), P.at_items.begin() + it.x))
       return fail("assembly: a tile's H entries");
   }
-  // every front's lower tiles exactly once, whatever the order (the tasks of
-  // a level are dealt to the XCDs in blocks, ea_xcd_order)
-  std::vector<std::vector<char>> seen(P.ns);
-  for (const int4& t : P.ea_tasks) {
-    const int s = t.x, ti = t.y >> 16, tj = t.y & 0xffff, nt = (P.m[s] + 63) / 64;
-    if (ti >= nt || tj > ti) return fail("assembly: a tile outside its front's lower triangle");
-    if (seen[s].empty()) seen[s].assign((size_t)nt * (nt + 1) / 2, 0);
-    char& k = seen[s][(size_t)ti * (ti + 1) / 2 + tj];
-    if (k) return fail("assembly: a tile listed twice");
-    k = 1;
+  return 0;
+}
+
+// Who writes a front first.  Every 64x64 lower tile of every front this rank
+// assembles (so every lower-trapezoid element: both kinds of task write their
+// tile whole) is written whole exactly once before any task reads it: by its
+// assembly tile (k_assemble_tile), or by a fused Schur task (syrk_gather: the
+// 64-tile task that is the first update of an update-matrix tile and forms it
+// from the children itself).  A fused task is tile-aligned and covers the
+// tile's columns, sits at or past w rounded up to 64, and no Schur task of an
+// earlier step or earlier in its step's list touches its tile; a plain Schur
+// task only touches tiles already written.  Both kinds list exactly the child
+// rectangles that land on their tile, children in order (brute force from the
+// extend-add maps).
+int check_first_writes(const pgo::CholPlan& P) {
+  if (P.syrk_gather.size() != P.syrk_tasks.size()) return fail("fused: gather records");
+  // 0: unwritten, 1: written by its assembly tile, 2: by its fused task, 3: updated since
+  std::vector<std::vector<char>> st(P.ns);
+  auto tile = [&](int s, int ti, int tj) -> char& {
+    const int nt = (P.m[s] + 63) / 64;
+    if (st[s].empty()) st[s].assign((size_t)nt * (nt + 1) / 2, 0);
+    return st[s][(size_t)ti * (ti + 1) / 2 + tj];
+  };
+  auto check_pairs = [&](int s, int ti, int tj, int first, int cnt) {
+    std::vector<int4> want;
+    for (int q = P.cptr[s]; q < P.cptr[s + 1]; q++) {
+      const int c = P.children[q], u = P.m[c] - P.w[c];
+      int ra = -1, rn = 0, ca = -1, cn = 0;
+      for (int a = 0; a < u; a++) {
+        const int r = 3 * P.ea_rel[P.ea_ptr[c] + a / 3] + a % 3;
+        if (r / 64 == ti && rn++ == 0) ra = a;
+        if (r / 64 == tj && cn++ == 0) ca = a;
+      }
+      if (rn && cn) want.push_back(make_int4(c, ra, ca, rn | (cn << 8)));
+    }
+    if (cnt != (int)want.size() || first < 0 || (size_t)first + cnt > P.ea_pairs.size()) return false;
+    for (int k = 0; k < cnt; k++) {
+      const int4 a = P.ea_pairs[first + k], b = want[k];
+      if (a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w) return false;
+    }
+    return true;
+  };
+  long long fused = 0, fused_pairs = 0;
+  for (const auto& lv : P.levels) {
+    for (int q = lv.ea_off[0]; q < lv.ea_off[0] + lv.ea_cnt[0]; q++) {
+      const int4 t = P.ea_tasks[q];
+      const int s = t.x, ti = t.y >> 16, tj = t.y & 0xffff, nt = (P.m[s] + 63) / 64;
+      if (ti >= nt || tj > ti) return fail("assembly: a tile outside its front's lower triangle");
+      char& k = tile(s, ti, tj);
+      if (k) return fail("assembly: a tile listed twice");
+      k = 1;
+      if (!check_pairs(s, ti, tj, t.z, t.w)) return fail("assembly: a tile's child rectangles");
+    }
+    for (const auto& ps : lv.panels)
+      for (int q = ps.syrk_off; q < ps.syrk_off + ps.syrk_cnt; q++) {
+        const int4 t = P.syrk_tasks[q];
+        const int2 g = P.syrk_gather[q];
+        const int s = t.x, row0 = t.y & pgo::kRowMask, clip = t.y >> pgo::kClipShift, c0 = t.z, m = P.m[s], w = P.w[s];
+        const int T = ps.syrk_tile;
+        const int colend = t.w < 0 ? std::min((ps.kb & ~(pgo::kKB - 1)) + pgo::kKB, w) : m;
+        const int cend = std::min({colend, c0 + (clip ? clip : T), m});
+        if (g.x >= 0) {
+          if (T != pgo::kTile || t.w != 0 || (row0 & 63) || (c0 & 63) || c0 < ((w + 63) & ~63) ||
+              cend != std::min(m, c0 + 64) || !pgo::front_packed(m, w))
+            return fail("fused: a task that is not a whole update-matrix 64-tile's first update");
+          char& k = tile(s, row0 / 64, c0 / 64);
+          if (k) return fail("fused: the tile was written or updated before its fused task");
+          k = 2;
+          if (!check_pairs(s, row0 / 64, c0 / 64, g.x, g.y)) return fail("fused: a tile's child rectangles");
+          fused++;
+          fused_pairs += g.y > 0;
+          continue;
+        }
+        for (int r0 = row0; r0 < std::min(row0 + T, m); r0 += 64)
+          for (int cb = c0 / 64; cb <= (cend - 1) / 64 && cb <= r0 / 64; cb++) {
+            char& k = tile(s, r0 / 64, cb);
+            if (!k) return fail("a Schur task reads a tile nothing has written");
+            k = 3;
+          }
+      }
   }
-  for (int s = 0; s < P.ns; s++)
-    for (char k : seen[s])
-      if (!k) return fail("assembly: a front's tile missing");
+  if (fused != P.fused_tiles || fused_pairs != P.fused_with_pairs) return fail("fused: the plan's counts");
+  for (const int4& t : P.ea_tasks)   // (a front's tile (0, 0) is never fused: the fronts this rank assembles)
+    if (t.y == 0)
+      for (char k : st[t.x])
+        if (!k) return fail("a front's tile is written by no task");
   return 0;
 }
 
@@ -317,7 +389,7 @@ int check_append(const Pattern& G, int n0, int ordering) {
     for (int k = Gn.row_ptr[n - 1]; k < Gn.row_ptr[n]; k++) pairs.push_back(make_int2(n - 1, Gn.col[k]));
     if (!pgo::chol_append(P, n, Gn.row_ptr, Gn.col, pairs, 1 << 30, 1e30)) return fail("append: refused");
     if (P.schedule_error) return fail("append: panel schedule bookkeeping");
-    if (check_assembly(P) || check_sources(P, Gn.row_ptr, Gn.col, G.n) || check_splice(P, Gn.row_ptr, Gn.col, G.n)) return 1;
+    if (check_assembly(P) || check_first_writes(P) || check_sources(P, Gn.row_ptr, Gn.col, G.n) || check_splice(P, Gn.row_ptr, Gn.col, G.n)) return 1;
     emulate_bind(P, Gn.row_ptr, Gn.col, G.n);   // (the next append splices)
     if (P.n != n || !pgo::chol_covers(P, n, Gn.row_ptr, Gn.col)) return fail("append: pattern not covered");
     for (int s = 0; s < P.ns; s++) {
@@ -372,7 +444,7 @@ int main() {
     if (P.ns <= 0 || P.flops <= 0) return fail("analysis");
     if (P.schedule_error) return fail("panel schedule bookkeeping");
     if (!pgo::chol_covers(P, G.n, G.row_ptr, G.col)) return fail("plan does not cover its own pattern");
-    if (check_assembly(P) || check_tiles(P) || check_sources(P, G.row_ptr, G.col)) return 1;
+    if (check_assembly(P) || check_first_writes(P) || check_tiles(P) || check_sources(P, G.row_ptr, G.col)) return 1;
     for (int size : {2, 4}) {
       std::vector<double> rf;
       double top = 0;
@@ -385,7 +457,7 @@ int main() {
         Q.part_rank = r;
         pgo::chol_analyze(Q, G.n, G.row_ptr, G.col);
         if (Q.ns != P.ns || Q.schedule_error) return fail("partitioned plan");
-        if (check_assembly(Q) || check_tiles(Q)) return 1;
+        if (check_assembly(Q) || check_first_writes(Q) || check_tiles(Q)) return 1;
       }
     }
     // a loop closure inside the existing fill: same fronts, new assembly lists
@@ -428,7 +500,17 @@ int main() {
     }
     pgo::CholPlan P;
     pgo::chol_analyze(P, G.n, G.row_ptr, G.col);
-    if (check_tiles(P)) return 1;
+    if (check_tiles(P) || check_first_writes(P)) return 1;
+    {   // PGO_FUSE_UPDATE=0: every tile back in the assembly lists, the same Schur tasks
+      setenv("PGO_FUSE_UPDATE", "0", 1);
+      pgo::CholPlan Q;
+      pgo::chol_analyze(Q, G.n, G.row_ptr, G.col);
+      unsetenv("PGO_FUSE_UPDATE");
+      if (P.fused_tiles <= 0 || P.fused_with_pairs <= 0 || Q.fused_tiles != 0 || Q.schedule_error ||
+          check_first_writes(Q) || Q.ea_tasks.size() != P.ea_tasks.size() + (size_t)P.fused_tiles ||
+          Q.syrk_tasks.size() != P.syrk_tasks.size() || Q.ea_pairs.size() != P.ea_pairs.size())
+        return fail("grid: the fused tiles against PGO_FUSE_UPDATE=0");
+    }
     for (int size : {2, 3, 4, 8})
       if (check_distributed(G, pgo::kOrderNd, size)) return 1;
     int maxw = 0;

@@ -2727,6 +2727,12 @@ int pgo_debug_plan(pgo_graph* g, double* out, int cap) {
   out[9] = (double)trsm;
   out[10] = (double)syrk;
   out[11] = (double)P.small_list.size();
+  // fused update-matrix tiles (pgo_chol.h syrk_gather): all; with a child
+  // rectangle; with more than one gather pass of them; clipped by the front's edge
+  out[12] = (double)P.fused_tiles;
+  out[13] = (double)P.fused_with_pairs;
+  out[14] = (double)P.fused_multipass;
+  out[15] = (double)P.fused_edge;
   int o = 16;
   for (const auto& lv : P.levels) {   // per level: fronts, max m, max blocks, panels, small fronts, syrk tiles
     if (o + 6 > cap) break;

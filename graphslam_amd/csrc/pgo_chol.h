@@ -93,6 +93,8 @@ struct PanelStep {                 // one 64-column panel kb of every big front 
   // each joined before the first step that touches it
   int far_cnt = 0, far_p0 = 0, far_np = 0;
   double far_flops = 0;            // ... their share of plain_flops
+  double gather_bytes = 0;         // algorithmic HBM bytes the step's fused tiles read from the children's
+                                   // update matrices (CholPlan::syrk_gather), reported with its 64-tile launch
   // k_step's flops by role (sdiag; col + prep updates; col solves): a step with
   // many diagonal tiles runs them as three launches instead (chol_factor)
   double diag_flops = 0, colupd_flops = 0, trsm_flops = 0;
@@ -186,7 +188,18 @@ struct CholPlan {
   std::vector<int4> bwd_part_tasks;  // (front, c0, r0, partial slot)
   int npart = 0;
   std::vector<int4> ea_tasks;      // (front, tile row << 16 | tile col, first pair, pairs): every 64x64
-                                   // lower tile of every front, per level (k_assemble_tile)
+                                   // lower tile of every front but the fused ones, per level (k_assemble_tile)
+  // Fused update-matrix tiles: a 64x64 tile of a blocked front's update matrix
+  // (column block at or past w rounded up to 64) holds no H entry, only its
+  // children's rectangles; where its first Schur update is a 64-tile task, that
+  // task forms the tile from the children itself instead of reading it back
+  // (syrk_lds_body), and the tile has no assembly task.  Per syrk task: (first
+  // pair, pairs) of the tile in ea_pairs, or (-1, 0): a plain read-modify-write.
+  // PGO_FUSE_UPDATE=0 (read at every plan): none.
+  std::vector<int2> syrk_gather;
+  // fused tiles; those with a child rectangle; with more than one gather pass
+  // of rectangles; clipped by the front's edge (pgo_debug_plan)
+  long long fused_tiles = 0, fused_with_pairs = 0, fused_multipass = 0, fused_edge = 0;
   std::vector<int2> at_iptr;       // per tile task: (first, count) of its H entries in at_items
   std::vector<int> at_items;       // H entries: asm target t >= 0, or ~pose (diagonal block + lambda)
   std::vector<int4> ea_pairs;      // (child, first row a0, first column b0, rows | columns << 8):
@@ -242,6 +255,7 @@ struct CholPlan {
   int *d_dg_front = nullptr, *d_dg_loc = nullptr, *d_perm = nullptr;
   int *d_small = nullptr, *d_level_fronts = nullptr, *d_potrf = nullptr;
   int4 *d_syrk = nullptr, *d_sdiag = nullptr, *d_col = nullptr;
+  int2* d_syrk_gather = nullptr;
   int2* d_at_iptr = nullptr;
   int* d_at_items = nullptr;
   int4 *d_xown = nullptr, *d_xforeign = nullptr, *d_xsol_own = nullptr, *d_xsol_foreign = nullptr;

@@ -38,6 +38,7 @@ struct CholDev {
   const int *m, *w, *voff, *rptr, *rows;
   const long long* foff;
   const int *cptr, *children, *ea_rel, *ea_ptr, *parent;
+  const int4* ea_pairs;            // child rectangles of the fused update-matrix tiles (syrk_lds_body)
   const int *asm_front, *asm_li, *asm_lj, *asm_ptr, *asm_src;
   const int *dg_front, *dg_loc, *perm;
   int* flag;
@@ -68,6 +69,7 @@ static CholDev dev_view(const CholPlan& P) {
   c.m = P.d_m; c.w = P.d_w; c.voff = P.d_voff; c.rptr = P.d_rptr; c.rows = P.d_rows; c.foff = P.d_foff;
   c.cptr = P.d_cptr; c.children = P.d_children; c.ea_rel = P.d_ea_rel; c.ea_ptr = P.d_ea_ptr;
   c.parent = P.d_parent;
+  c.ea_pairs = P.d_ea_pairs;
   c.asm_front = P.d_asm_front; c.asm_li = P.d_asm_li; c.asm_lj = P.d_asm_lj; c.asm_ptr = P.d_asm_ptr;
   c.asm_src = P.d_asm_src; c.dg_front = P.d_dg_front; c.dg_loc = P.d_dg_loc; c.perm = P.d_perm;
   c.flag = P.d_flag;
@@ -1511,12 +1513,21 @@ __device__ __forceinline__ void syrk_tile64(const CholDev& c, const int4 t, int 
 // per chunk, issued one chunk ahead of the MFMAs).  Low register count, so
 // several workgroups per CU hide the load latency.
 // smem: 4 * 16 * 68 doubles (Sr[2], Sc[2])
+// g: the task's gather record (CholPlan::syrk_gather).  g.x >= 0: a fused
+// update-matrix tile, which no launch has written yet.  In place of the read
+// of C the task forms the tile as the assembly would have -- 0 plus the
+// children's elements that land on it, rectangles g.x .. g.x + g.y of ea_pairs
+// in child order, k_assemble_tile's sum term for term -- with the row and
+// column maps of kAsmPairs rectangles at a time in the staging buffers (dead
+// after the k loop); further passes go on in the same registers.
 // KC: panel columns staged per chunk (16; 32 halves the round trips with the
 // same 4-deep MFMA steps in the same k order -- bitwise the same tile -- but
 // measured no faster, profiles/r05n_syrk_ubench.txt)
 template <int KC = 16>
-__device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, int kb, double* smem) {
+__device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, int kb, double* smem,
+                                              const int2 g = make_int2(-1, 0)) {
   constexpr int LD = 64 + 4, NQ = KC / 4;
+  static_assert(4 * KC * LD * sizeof(double) >= kAsmPairs * 64 * 16 + kAsmPairs * 8, "gather maps in the staging buffers");
   double(*Sr)[KC * LD] = reinterpret_cast<double(*)[KC * LD]>(smem);
   double(*Sc)[KC * LD] = reinterpret_cast<double(*)[KC * LD]>(smem + 2 * KC * LD);
   const int s = t.x, row0 = t.y & kRowMask, col0 = t.z, clip = t.y >> kClipShift;
@@ -1603,10 +1614,72 @@ __device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, in
     if (ch + 1 < nch) stash(b ^ 1);
     __syncthreads();
   }
-  if (!active) return;
-  // (the C tile's loads after the k loop: issued before it, 117 vs 110 us on
-  // the 4096-row outer update, profiles/r04g_syrk_ubench.txt)
-  load_c();
+  if (g.x >= 0) {   // (workgroup-uniform; the inactive waves of a diagonal tile help build the maps)
+    int(*rmap)[64] = reinterpret_cast<int(*)[64]>(smem);                          // child row on tile row i (-1: none)
+    int(*cmap)[64] = rmap + kAsmPairs;                                            // child column on tile column j
+    long long(*coff)[64] = reinterpret_cast<long long(*)[64]>(cmap + kAsmPairs);  // ... its offset in the child front
+    long long* pbase = &coff[kAsmPairs][0];                                       // the child front's base
+#pragma unroll
+    for (int p = 0; p < 8; p++) cold[p][0] = cold[p][1] = 0.0;
+    const int i0 = qi + (l & 15);
+    for (int k0p = 0; k0p < g.y; k0p += kAsmPairs) {
+      const int np = min(kAsmPairs, g.y - k0p);
+      if (k0p) __syncthreads();   // the previous pass's maps are read
+      for (int q = tid; q < kAsmPairs * 64; q += 256) {
+        rmap[q >> 6][q & 63] = -1;
+        cmap[q >> 6][q & 63] = -1;
+      }
+      __syncthreads();
+      for (int q = tid; q < np * 128; q += 256) {   // child rectangles -> row / column maps (as k_assemble_tile)
+        const int kk = q >> 7, h = q & 127;
+        const int4 pr = c.ea_pairs[g.x + k0p + kk];
+        const int ch = pr.x, nr = pr.w & 0xff, nc = pr.w >> 8;
+        const int* __restrict__ rel = c.ea_rel + c.ea_ptr[ch];
+        if (h < 64) {
+          if (h < nr) {
+            const int a = pr.y + h;
+            rmap[kk][3 * rel[a / 3] + a % 3 - row0] = a;
+          }
+          if (h == 0) pbase[kk] = c.foff[ch];
+        } else if (h - 64 < nc) {
+          const int b = pr.z + h - 64, mc = c.m[ch], wc = c.w[ch];
+          const int pc = 3 * rel[b / 3] + b % 3 - col0;
+          cmap[kk][pc] = b;
+          coff[kk][pc] = fcol_off(mc, front_packed(mc, wc), wc + b) + wc;
+        }
+      }
+      __syncthreads();
+      if (active) {
+        // the children's elements, in child order; a child's 8 loads of one
+        // row in flight (the two rows one after the other: the 16 together cost
+        // the kernel a workgroup per CU in registers)
+#pragma unroll
+        for (int h = 0; h < 2; h++)
+#pragma unroll 1
+          for (int kk = 0; kk < np; kk++) {
+            const int a = rmap[kk][i0 + 16 * h];
+            const double* __restrict__ Fch = c.F + pbase[kk] + a;
+            double add[8];
+            bool in[8];
+#pragma unroll
+            for (int p = 0; p < 8; p++) {
+              const int j = qj + 4 * p + lk, b = a >= 0 ? cmap[kk][j] : -1;
+              in[p] = b >= 0 && b <= a;
+              add[p] = in[p] ? Fch[coff[kk][j]] : 0.0;
+            }
+#pragma unroll
+            for (int p = 0; p < 8; p++)
+              if (in[p]) cold[p][h] += add[p];
+          }
+      }
+    }
+    if (!active) return;
+  } else {
+    if (!active) return;
+    // (the C tile's loads after the k loop: issued before it, 117 vs 110 us on
+    // the 4096-row outer update, profiles/r04g_syrk_ubench.txt)
+    load_c();
+  }
 #pragma unroll
   for (int p = 0; p < 8; p++)
 #pragma unroll
@@ -1616,10 +1689,12 @@ __device__ __forceinline__ void syrk_lds_body(const CholDev& c, const int4 t, in
     }
 }
 
-__global__ __launch_bounds__(256) void k_panel_syrk_lds(CholDev c, const int4* __restrict__ tasks, int kb) {
+// gather: the tasks' gather records, or null (none of them fused)
+__global__ __launch_bounds__(256, 4) void k_panel_syrk_lds(CholDev c, const int4* __restrict__ tasks,
+                                                        const int2* __restrict__ gather, int kb) {
   lane_offset(c);
   __shared__ __attribute__((aligned(16))) double smem[4 * 16 * 68];
-  syrk_lds_body(c, tasks[blockIdx.x], kb, smem);
+  syrk_lds_body(c, tasks[blockIdx.x], kb, smem, gather ? gather[blockIdx.x] : make_int2(-1, 0));
 }
 
 // Schur update of a diagonal 64x64 tile into LDS: Ts (ld 65, lower) = C - P P^T,
@@ -1915,12 +1990,14 @@ __global__ __launch_bounds__(256) void k_first_trsm(CholDev c, const int4* __res
 //                       its diagonal tile: Schur update with panel kb (kept in
 //                       LDS), then, once the diagonal inverse is published,
 //                       solved against it (trsm_rows)
-//   the rest            the other Schur-update tiles (syrk_lds_body)
+//   the rest            the other Schur-update tiles (syrk_lds_body; tgather:
+//                       their gather records)
 // The diagonal workgroups come first in dispatch order, so every waiting
 // workgroup waits on a workgroup dispatched before it.
 __global__ __launch_bounds__(256, 2) void k_step(CholDev c, const int4* __restrict__ sdiag, int nsd,
                                               const int4* __restrict__ col, int ncol, int nprep,
-                                              const int4* __restrict__ tiles, int kb, int slot) {
+                                              const int4* __restrict__ tiles, const int2* __restrict__ tgather,
+                                              int kb, int slot) {
   lane_offset(c);
   __shared__ __attribute__((aligned(16))) double smem[kDiagSmem];
   const int b = blockIdx.x;
@@ -1946,7 +2023,7 @@ __global__ __launch_bounds__(256, 2) void k_step(CholDev c, const int4* __restri
     syrk_lds_body(c, col[b - nsd], kb, smem);
     return;
   }
-  syrk_lds_body(c, tiles[b - nsd - ncol - nprep], kb, smem);
+  syrk_lds_body(c, tiles[b - nsd - ncol - nprep], kb, smem, tgather[b - nsd - ncol - nprep]);
 }
 
 // A split step's diagonal tiles (k_step's [0, nsd) role alone): updated,
@@ -2744,6 +2821,7 @@ static hipError_t upload_index(CholPlan& P, hipStream_t s) {
   blob_add(it, &P.d_bwd_pref, P.bwd_pref);
   blob_add(it, &P.d_bwd_part, P.bwd_part_tasks);
   blob_add(it, &P.d_syrk, P.syrk_tasks);
+  blob_add(it, &P.d_syrk_gather, P.syrk_gather);
   blob_add(it, &P.d_sdiag, P.sdiag_tasks);
   blob_add(it, &P.d_col, P.col_tasks);
   blob_add(it, &P.d_xown, own);
@@ -3085,13 +3163,19 @@ static hipError_t factor_level_panels(const CholPlan& P, const CholDev& c, const
     }
     CH_TRY(xpanels(ps.xfirst));
     const int4* tiles = (const int4*)(P.d_syrk + ps.syrk_off);
+    const int2* tgather = (const int2*)(P.d_syrk_gather + ps.syrk_off);
     const int nin = ps.syrk_inline && !kn.off("plain") ? ps.syrk_cnt : 0;
     const bool apart = ps.syrk_cnt > 0 && !ps.syrk_inline && !kn.off("plain");   // plain tiles in their own launch
     const bool step = ps.sdiag_cnt + ps.col_cnt + ps.prep_cnt + nin > 0 && !kn.off("step");
+    // (bytes: what the launch's fused tiles gather from the children, the traffic
+    // that left k_assemble_tile's count; the whole step's with its near tiles)
     auto plain = [&](hipStream_t st, int first, int cnt, double flops) {
-      const bool big = ps.syrk_tile == kBigTile;
-      launch(prof, big ? kFamPanelSyrk128 : kFamPanelSyrk, [&] { return make_double2(flops * nb, 0); },
-             big ? k_panel_syrk128 : k_panel_syrk_lds, dim3(cnt, nb), B256, 0, st, c, tiles + first, ps.kb);
+      auto cost = [&] { return make_double2(flops * nb, first == 0 ? ps.gather_bytes * nb : 0.0); };
+      if (ps.syrk_tile == kBigTile)
+        launch(prof, kFamPanelSyrk128, cost, k_panel_syrk128, dim3(cnt, nb), B256, 0, st, c, tiles + first, ps.kb);
+      else
+        launch(prof, kFamPanelSyrk, cost, k_panel_syrk_lds, dim3(cnt, nb), B256, 0, st, c, tiles + first,
+               tgather + first, ps.kb);
     };
     if (apart) {   // on the side stream (beside k_step, behind the earlier plains)
       CH_TRY(hipEventRecord(P.evs[P.kEvForkPlain], s));
@@ -3111,10 +3195,10 @@ static hipError_t factor_level_panels(const CholPlan& P, const CholDev& c, const
       CH_TRY(hipEventRecord(P.evs[P.kEvForkMain], s));
       CH_TRY(hipStreamWaitEvent(P.side5, P.evs[P.kEvForkMain], 0));
       launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.colupd_flops * nb, 0); }, k_panel_syrk_lds,
-             dim3(ps.col_cnt + ps.prep_cnt, nb), B256, 0, P.side5, c, cupd, ps.kb);
+             dim3(ps.col_cnt + ps.prep_cnt, nb), B256, 0, P.side5, c, cupd, (const int2*)nullptr, ps.kb);
       if (nin)
-        launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.plain_flops * nb, 0); }, k_panel_syrk_lds,
-               dim3(nin, nb), B256, 0, P.side5, c, tiles, ps.kb);
+        launch(prof, kFamPanelSyrk, [&] { return make_double2(ps.plain_flops * nb, ps.gather_bytes * nb); },
+               k_panel_syrk_lds, dim3(nin, nb), B256, 0, P.side5, c, tiles, tgather, ps.kb);
       CH_TRY(hipEventRecord(P.evs[P.kEvJoinSide2], P.side5));
       launch(prof, kFamStepDiag, [&] { return make_double2(ps.diag_flops * nb, 0); }, k_step_diag,
              dim3(ps.sdiag_cnt, nb), B256, 0, s, c, (const int4*)(P.d_sdiag + ps.sdiag_off), ps.kb);
@@ -3122,10 +3206,10 @@ static hipError_t factor_level_panels(const CholPlan& P, const CholDev& c, const
       launch(prof, kFamColTrsm, [&] { return make_double2(ps.trsm_flops * nb, 0); }, k_first_trsm,
              dim3(ps.col_cnt, nb), B256, 0, s, c, cupd);
     } else if (step)
-      launch(prof, kFamStep, [&] { return make_double2(ps.step_flops * nb, 0); }, k_step,
+      launch(prof, kFamStep, [&] { return make_double2(ps.step_flops * nb, nin ? ps.gather_bytes * nb : 0.0); }, k_step,
              dim3(ps.sdiag_cnt + ps.col_cnt + ps.prep_cnt + nin, nb), B256, 0, s, c,
              (const int4*)(P.d_sdiag + ps.sdiag_off), ps.sdiag_cnt, cols + ps.fcol_cnt, ps.col_cnt, ps.prep_cnt,
-             tiles, ps.kb,
+             tiles, tgather, ps.kb,
              kn.stamps && li + 1 == P.levels.size() && ps.kb / kNB < kMaxStampSlots ? ps.kb / kNB : -1);
     if (apart) {   // (never on the main stream: an earlier plain may still run on P.side)
       const int nnear = ps.syrk_cnt - ps.far_cnt;

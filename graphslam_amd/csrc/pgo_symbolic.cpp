@@ -389,6 +389,8 @@ struct LevelLists {
   std::vector<int> small_list, level_fronts, potrf_list;
   std::vector<int4> syrk_tasks, sdiag_tasks, col_tasks, bwd_tasks, bwdc_tasks, bwd_part_tasks, ea_tasks, ea_pairs;
   std::vector<int2> bwd_pref;
+  std::vector<int2> syrk_gather;   // per syrk task (fuse_level)
+  long long fused = 0, fused_with_pairs = 0, fused_multipass = 0, fused_edge = 0;
   std::vector<XExchange> xchg;
   std::vector<int4> xp_tasks;
   std::vector<long long> xp_loff, xp_lstride;
@@ -397,6 +399,8 @@ struct LevelLists {
   bool schedule_error = false;
   // empty again, capacity kept
   void reset() {
+    syrk_gather.clear();
+    fused = fused_with_pairs = fused_multipass = fused_edge = 0;
     for (auto* v : {&small_list, &level_fronts, &potrf_list}) v->clear();
     for (auto* v : {&syrk_tasks, &sdiag_tasks, &col_tasks, &bwd_tasks, &bwdc_tasks, &bwd_part_tasks, &ea_tasks, &ea_pairs,
                     &xp_tasks})
@@ -640,8 +644,8 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
         st.cnt = (int)S.bwd_tasks.size() - st.off;
         lv.bwd.push_back(st);
       }
-      // assembly: one task per 64x64 tile of every front's lower triangle, which
-      // it writes whole: its H entries (+ lambda on the diagonal), then the
+      // assembly: one task per 64x64 tile of every front's lower triangle (the
+      // fused ones leave the list in fuse_level), which it writes whole: its H entries (+ lambda on the diagonal), then the
       // update-matrix elements of the front's children in order (fixed
       // summation order, no atomics), each child contributing a rectangle of its
       // update matrix (child rows [a0, a0+nr) x columns [b0, b0+nc), the rows /
@@ -693,8 +697,7 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
               S.ea_pairs[base + tpos[k]++] = make_int4(runs[i].x, runs[i].z, runs[j].z, runs[i].w | (runs[j].w << 8));
             }
       }
-      ea_xcd_order(S.ea_tasks, (size_t)lv.ea_off.back());
-      lv.ea_cnt.push_back((int)S.ea_tasks.size() - lv.ea_off.back());
+      // (fuse_level takes the fused tiles out, orders the rest and sets ea_cnt)
       return;
     }
     // part 1: the factorisation lists (small-front classes, blocked panel steps)
@@ -1117,6 +1120,77 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
       fprintf(stderr, "  level %d: %.2f + %.2f ms (%zu fronts)\n", L, lms[2 * L], lms[2 * L + 1], bylevel[L].size());
     phase("levels");
   }
+  // Fused update-matrix tiles (pgo_chol.h syrk_gather), once both parts of a
+  // level are there.  A tile (ti, tj) of a blocked front with 64 tj >= w rounded
+  // up to 64 holds no H entry (chol_assembly checks it).  Its columns' first
+  // Schur update is the task that finds applied == 0 and is not inner: k0 word
+  // 0.  Where that is a 64-tile task of a front that is not distributed, the
+  // task takes the tile's child rectangles and the tile leaves the assembly
+  // list; its pairs stay in ea_pairs.  Such a task (r0, c0) is assembly tile
+  // (r0 / 64, c0 / 64) exactly: gen_tiles aligns a range's tiles to the
+  // 64-column blocks after a narrow opening tile (the block straddling w: not
+  // fused), rows run from the column down in steps of 64, and the range ends
+  // at m.  Asserted here (schedule_error).  A later update of the same columns
+  // (a wide front's next kKB block end: k0 > 0) stays a plain read-modify-write,
+  // and so does every tile of a 128-tile step.  Then the XCD order of what is
+  // left, as before (PGO_FUSE_UPDATE=0: all of it).
+  const bool fuse_on = !(getenv("PGO_FUSE_UPDATE") && atoi(getenv("PGO_FUSE_UPDATE")) == 0);
+  auto fuse_level = [&](int L, LevelLists& S) {
+    CholLevel& lv = P.levels[L];
+    const bool dist = dtop && L >= P.split;
+    const size_t e0 = (size_t)lv.ea_off.back();
+    S.syrk_gather.assign(S.syrk_tasks.size(), make_int2(-1, 0));
+    if (fuse_on && !dist && !S.syrk_tasks.empty()) {
+      // a front's tile tasks: contiguous from its tile (0, 0), tile (ti, tj) at ti (ti + 1) / 2 + tj
+      std::vector<std::pair<int, int>> fstart;
+      for (size_t q = e0; q < S.ea_tasks.size(); q++)
+        if (S.ea_tasks[q].y == 0) fstart.emplace_back(S.ea_tasks[q].x, (int)q);
+      std::sort(fstart.begin(), fstart.end());
+      std::vector<char> gone(S.ea_tasks.size(), 0);
+      // (elements of a child rectangle inside the child's lower triangle, as level_at_bytes counts them)
+      auto G = [](long long x, long long c) -> long long {
+        if (x <= 0) return 0;
+        return x <= c ? x * (x + 1) / 2 : c * (c + 1) / 2 + (x - c) * c;
+      };
+      for (PanelStep& ps : lv.panels) {
+        if (ps.syrk_tile != kTile) continue;
+        for (int q = ps.syrk_off; q < ps.syrk_off + ps.syrk_cnt; q++) {
+          const int4 t = S.syrk_tasks[q];
+          const int s = t.x, r0 = t.y & kRowMask, clip = t.y >> kClipShift, c0 = t.z, m = P.m[s];
+          if (t.w != 0 || c0 < ((P.w[s] + 63) & ~63)) continue;
+          const auto it = std::lower_bound(fstart.begin(), fstart.end(), std::make_pair(s, 0));
+          const int ti = r0 >> 6, tj = c0 >> 6;
+          const size_t e = it == fstart.end() ? S.ea_tasks.size() : (size_t)it->second + (size_t)ti * (ti + 1) / 2 + tj;
+          const bool whole = !(r0 & 63) && !(c0 & 63) && std::min(m, c0 + (clip ? clip : kTile)) == std::min(m, c0 + 64);
+          if (!whole || e >= S.ea_tasks.size() || S.ea_tasks[e].x != s || S.ea_tasks[e].y != ((ti << 16) | tj) || gone[e]) {
+            if (getenv("PGO_SCHED_DEBUG") && !S.schedule_error)
+              fprintf(stderr, "sched: fused tile front %d w %d m %d task (%d, %d) clip %d\n", s, P.w[s], m, r0, c0, clip);
+            S.schedule_error = true;
+            continue;
+          }
+          gone[e] = 1;
+          for (int k = 0; k < S.ea_tasks[e].w; k++) {
+            const int4 pr = S.ea_pairs[S.ea_tasks[e].z + k];
+            const long long nr = pr.w & 0xff, ncl = pr.w >> 8, d = pr.y - pr.z + 1;
+            ps.gather_bytes += 8.0 * (double)(G(d + nr - 1, ncl) - G(d - 1, ncl));
+          }
+          S.syrk_gather[q] = make_int2(S.ea_tasks[e].z, S.ea_tasks[e].w);
+          S.fused++;
+          S.fused_with_pairs += S.ea_tasks[e].w > 0;
+          S.fused_multipass += S.ea_tasks[e].w > 16;   // (kAsmPairs rectangles per gather pass)
+          S.fused_edge += r0 + 64 > m || c0 + 64 > m;
+        }
+      }
+      size_t o = e0;
+      for (size_t q = e0; q < S.ea_tasks.size(); q++)
+        if (!gone[q]) S.ea_tasks[o++] = S.ea_tasks[q];
+      S.ea_tasks.resize(o);
+    }
+    ea_xcd_order(S.ea_tasks, e0);
+    lv.ea_cnt.push_back((int)S.ea_tasks.size() - lv.ea_off.back());
+  };
+  plan_parallel(nl, [&](int L) { fuse_level(L, out[L]); });
+  phase("fuse");
   // merge: level-relative offsets and indices made absolute; the level lists
   // copied into place level by level on the pool (offsets from a serial pass)
   struct Base {
@@ -1155,6 +1229,7 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
   resize_room(P.level_fronts, tot.level_fronts);
   resize_room(P.potrf_list, tot.potrf_list);
   resize_room(P.syrk_tasks, tot.syrk_tasks);
+  resize_room(P.syrk_gather, tot.syrk_tasks);
   resize_room(P.sdiag_tasks, tot.sdiag_tasks);
   resize_room(P.col_tasks, tot.col_tasks);
   resize_room(P.bwd_tasks, tot.bwd_tasks);
@@ -1181,6 +1256,8 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
     lv.bwdc.off += (int)b.bwdc_tasks;
     for (int& o : lv.ea_off) o += (int)b.ea_tasks;
     for (int4& t : S.ea_tasks) t.z += (int)b.ea_pairs;
+    for (int2& g : S.syrk_gather)
+      if (g.x >= 0) g.x += (int)b.ea_pairs;
     for (SmallClass& sc : lv.small) sc.off += (int)b.small_list;
     for (PanelStep& ps : lv.panels) {
       ps.potrf_off += (int)b.potrf_list;
@@ -1197,6 +1274,7 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
     put(P.level_fronts, b.level_fronts, S.level_fronts);
     put(P.potrf_list, b.potrf_list, S.potrf_list);
     put(P.syrk_tasks, b.syrk_tasks, S.syrk_tasks);
+    put(P.syrk_gather, b.syrk_tasks, S.syrk_gather);
     put(P.sdiag_tasks, b.sdiag_tasks, S.sdiag_tasks);
     put(P.col_tasks, b.col_tasks, S.col_tasks);
     put(P.bwd_tasks, b.bwd_tasks, S.bwd_tasks);
@@ -1211,7 +1289,12 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
     put(P.xp_lstride, b.xp_lstride, S.xp_lstride);
   });
   P.syrk_flops = 0;
+  P.fused_tiles = P.fused_with_pairs = P.fused_multipass = P.fused_edge = 0;
   for (int L = 0; L < nl; L++) {
+    P.fused_tiles += out[L].fused;
+    P.fused_with_pairs += out[L].fused_with_pairs;
+    P.fused_multipass += out[L].fused_multipass;
+    P.fused_edge += out[L].fused_edge;
     for (const PanelStep& ps : P.levels[L].panels) P.syrk_flops += ps.plain_flops;
     P.xp_rslot = std::max(P.xp_rslot, out[L].xp_rslot);
     P.schedule_error = P.schedule_error || out[L].schedule_error;
@@ -1778,6 +1861,14 @@ void chol_assembly(CholPlan& P, const std::vector<int>& row_ptr, const std::vect
     }
   });
   lap("tile ptrs");
+  // a fused tile has no assembly task: it must hold no H entry
+  for (size_t q = 0; q < P.syrk_gather.size(); q++) {
+    if (P.syrk_gather[q].x < 0) continue;
+    const int4 t = P.syrk_tasks[q];
+    const int ti = (t.y & kRowMask) >> 6, tj = t.z >> 6, key = ti * (ti + 1) / 2 + tj;
+    const int* c = fcnt.data() + kbase[t.x];
+    if (c[key + 1] != c[key]) P.schedule_error = true;
+  }
   // (the levels' k_assemble_tile bytes: on first use, level_at_bytes)
   for (CholLevel& lv : P.levels) lv.at_bytes = -1.0;
 }

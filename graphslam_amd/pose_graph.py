@@ -399,7 +399,8 @@ class PoseGraph:
         out = np.zeros(cap)
         self._check(self._L.pgo_debug_plan(self._h, L.dptr(out), cap))
         keys = ["supernodes", "levels", "nnz_l", "factor_flops", "syrk_flops", "front_doubles",
-                "launches_factor", "launches_solve", "max_front", "trsm_tasks", "syrk_tiles", "small_fronts"]
+                "launches_factor", "launches_solve", "max_front", "trsm_tasks", "syrk_tiles", "small_fronts",
+                "fused_tiles", "fused_with_children", "fused_multipass", "fused_edge"]
         summary = {k: out[i] for i, k in enumerate(keys)}
         nl = int(out[1])
         lv = out[16:16 + 6 * nl].reshape(-1, 6)

@@ -454,7 +454,10 @@ int pgo_debug_solve(pgo_graph *g, double lambda, const pgo_params *params, doubl
 /* Host-only symbolic analysis of the current graph (no device needed):
  * out[0..11] = supernodes, levels, nnz(L), factor flops, Schur-update flops,
  * front doubles, launches per factorisation, launches per solve, max front,
- * trsm tasks, syrk tiles, small fronts; from out[16], 6 per level (leaves first):
+ * trsm tasks, syrk tiles, small fronts; out[12..15] = update-matrix tiles formed
+ * by their first Schur update instead of the tile assembly (PGO_FUSE_UPDATE=0:
+ * none): all, with a child rectangle, with more than 16 of them, clipped by
+ * their front's edge; from out[16], 6 per level (leaves first):
  * fronts, max m, max 64-blocks, panel steps, small fronts, syrk tiles. */
 int pgo_debug_plan(pgo_graph *g, double *out, int cap);
 /* Host-only: the subtree partition the PGO_MULTI_PARTITION factorisation
