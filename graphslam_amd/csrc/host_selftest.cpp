@@ -4,16 +4,21 @@
 // graphslam_amd/csrc asan-host`) exercises its memory accesses --
 // nested-dissection and AMD orderings, supernodes, level schedule, panel steps,
 // the assembly lists, the subtree partition for 2 and 4 ranks, the incremental
-// paths (chol_covers / chol_assembly, a caller-given ordering).  No GPU calls.
+// paths (chol_covers / chol_assembly, a caller-given ordering) -- and the graph
+// structure module (pgo_structure.cpp): the plan's sources bound through its
+// bind, in-place appends against rebuilds, the owner-bit transitions.  No GPU calls.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <tuple>
 #include <random>
 #include <vector>
 
 #include "pgo_chol.h"
+#include "pgo_structure.h"
 
 namespace {
 
@@ -62,7 +67,18 @@ Pattern make_pattern(int n, int lc, unsigned seed, const std::vector<std::pair<i
   return P;
 }
 
-constexpr int kDupIds = 8;   // parallel factors per pose pair the emulated bind tells apart
+// the pattern restricted to poses [0, n)
+Pattern restrict_pattern(const Pattern& G, int n) {
+  Pattern R;
+  R.n = n;
+  R.row_ptr.assign(1, 0);
+  for (int i = 0; i < n; i++) {
+    for (int k = G.row_ptr[i]; k < G.row_ptr[i + 1]; k++)
+      if (G.col[k] < n) R.col.push_back(G.col[k]);
+    R.row_ptr.push_back((int)R.col.size());
+  }
+  return R;
+}
 
 int fail(const char* m) {
   std::fprintf(stderr, "host_selftest: %s\n", m);
@@ -266,11 +282,13 @@ int check_first_writes(const pgo::CholPlan& P) {
 // of the permuted lower triangle (i > j) lists exactly the slots of one end of
 // the block -- as many as row perm[i] holds to column perm[j] -- and every
 // slot of the lower triangle is listed once.
-// (sources: ~slot unbound; bound ones -- bind emulated by emulate_bind, ids
-// (a * idn + b) * kDupIds + k of the k-th parallel factor of the pose pair
-// a < b -- checked against the block's poses, and a target's parallel
-// factors in their slot order, the summation order)
-int check_sources(const pgo::CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& col, int idn = 0) {
+// (sources: ~slot unbound; bound ones -- device factor indices, bound through
+// `S`, the structure the pattern came from -- checked against the block's
+// poses, and a target's parallel factors ascending: their slot order, the
+// summation order.  With as many sources as the block has slots that is every
+// factor of the pose pair, in device order.)
+int check_sources(const pgo::CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& col,
+                  const pgo::GraphStructure* S = nullptr) {
   long long total = 0, want = 0;
   for (size_t g = 0; g < P.asm_front.size(); g++) {
     const int s = P.asm_front[g], j = P.sfirst[s] + P.asm_lj[g], i = P.rows[P.rptr[s] + P.asm_li[g]];
@@ -281,9 +299,12 @@ int check_sources(const pgo::CholPlan& P, const std::vector<int>& row_ptr, const
     if (P.asm_ptr[g + 1] - P.asm_ptr[g] != cnt) return fail("assembly: a target's source count");
     for (int q = P.asm_ptr[g]; q < P.asm_ptr[g + 1]; q++) {
       if (P.asm_src[q] >= 0) {   // bound: the factor id
-        if (!idn || P.asm_src[q] / kDupIds != std::min(a, b) * idn + std::max(a, b))
+        if (!S || P.asm_src[q] >= S->ne()) return fail("assembly: a bound source that is no factor");
+        const int2 f = S->eij[P.asm_src[q]];
+        if (std::min(f.x, f.y) != std::min(a, b) || std::max(f.x, f.y) != std::max(a, b))
           return fail("assembly: a bound source off its block");
-        if (P.asm_src[q] % kDupIds != q - P.asm_ptr[g]) return fail("assembly: parallel factors out of slot order");
+        if (q > P.asm_ptr[g] && (P.asm_src[q - 1] < 0 || P.asm_src[q] <= P.asm_src[q - 1]))
+          return fail("assembly: parallel factors out of slot order");
         continue;
       }
       const int k = ~P.asm_src[q];
@@ -314,46 +335,59 @@ int check_tiles(const pgo::CholPlan& P) {
   return 0;
 }
 
-// the pattern restricted to poses [0, n)
-Pattern restrict_pattern(const Pattern& G, int n) {
-  Pattern R;
-  R.n = n;
-  R.row_ptr.assign(1, 0);
-  for (int i = 0; i < n; i++) {
-    for (int k = G.row_ptr[i]; k < G.row_ptr[i + 1]; k++)
-      if (G.col[k] < n) R.col.push_back(G.col[k]);
-    R.row_ptr.push_back((int)R.col.size());
+// ---- the graph structure module (pgo_structure.h) and the plan bound through it ----
+
+// A pose graph as the library's handle holds it: factors in user order with
+// their information (values of mixed magnitude, so the order of Dc's sums shows).
+struct TestGraph {
+  int n = 0;
+  std::vector<int2> e;
+  std::vector<int> pv;
+  std::vector<double> eom;
+  void add(int a, int b) {
+    e.push_back(make_int2(a, b));
+    for (int q = 0; q < 6; q++) eom.push_back(1.0 / (3.0 + (double)(eom.size() % 97)) + 1e-7 * (double)eom.size());
   }
-  return R;
+};
+
+pgo::GraphStructure built(const TestGraph& g) {
+  pgo::GraphStructure S;
+  S.build(g.n, g.e, g.pv, g.eom.data(), true);
+  return S;
 }
 
-// The host's bind (pgo_api.cpp bind_plan) emulated: every unbound source ~k
-// becomes a factor id, (a * idn + b) * kDupIds + j for the j-th slot of row r
-// to column c (pose pair a < b of {r, c}) -- a factor index in the library:
-// equal for both slots of a factor (a row lists a pair's parallel factors in
-// device order from either end), distinct between parallel factors, so a
-// splice that reorders them inside a target shows.
-void emulate_bind(pgo::CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& col, int idn) {
+// the factors of make_pattern's graph (odometry i -> i + 1, closures a -> b < a,
+// every lc / dups-th closure twice: a parallel factor)
+TestGraph make_edges(int n, int lc, unsigned seed, int dups) {
+  std::mt19937 rng(seed);
+  TestGraph g;
+  g.n = n;
+  for (int i = 0; i + 1 < n; i++) g.add(i, i + 1);
+  for (int q = 0; q < lc; q++) {
+    const int a = 20 + (int)(rng() % (unsigned)(n - 20));
+    g.add(a, (int)(rng() % (unsigned)(a - 10)));
+  }
+  for (int q = 0; dups > 0 && q < lc; q += std::max(1, lc / dups)) g.add(g.e[n - 1 + q].x, g.e[n - 1 + q].y);
+  return g;
+}
+
+// As bind_plan does: owner bits through the module, then every unbound source
+// ~slot becomes its factor's device index.
+void remap_sources(pgo::CholPlan& P, const pgo::GraphStructure& S) {
   for (int& x : P.asm_src)
-    if (x < 0) {
-      const int k = ~x;
-      const int r = (int)(std::upper_bound(row_ptr.begin(), row_ptr.end(), k) - row_ptr.begin()) - 1;
-      int j = 0;
-      for (int q = row_ptr[r]; q < k; q++) j += col[q] == col[k];
-      x = (std::min(r, col[k]) * idn + std::max(r, col[k])) * kDupIds + j;
-    }
+    if (x < 0) x = S.codes()[~x] >> 2;
   P.asm_bound = true;
 }
 
 // The spliced assembly targets of an append equal a rebuild of the same plan,
 // once both are bound.
-int check_splice(const pgo::CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& col, int idn) {
+int check_splice(const pgo::CholPlan& P, const pgo::GraphStructure& S) {
   pgo::CholPlan R = P;
   R.asm_splice = false;
-  pgo::chol_assembly(R, row_ptr, col);
-  emulate_bind(R, row_ptr, col, idn);
+  pgo::chol_assembly(R, S.row_ptr, S.slot_col);
+  remap_sources(R, S);
   pgo::CholPlan Q = P;
-  emulate_bind(Q, row_ptr, col, idn);
+  remap_sources(Q, S);
   if (Q.asm_front != R.asm_front || Q.asm_li != R.asm_li || Q.asm_lj != R.asm_lj || Q.asm_ptr != R.asm_ptr ||
       Q.asm_src != R.asm_src || Q.at_items != R.at_items || Q.at_iptr.size() != R.at_iptr.size())
     return fail("append: spliced assembly lists differ from a rebuild");
@@ -363,35 +397,53 @@ int check_splice(const pgo::CholPlan& P, const std::vector<int>& row_ptr, const 
 }
 
 // The incremental symbolic update (chol_append): poses appended one at a time
-// to a plan of the first n0 poses.  After each: the schedule is consistent,
-// every front's below rows sit in its parent at the extend-add map's index, the
-// sizes match the row lists, and the structure holds the exact fill of the
-// plan's own ordering (a fresh analysis on P.perm) and the whole pattern.
-int check_append(const Pattern& G, int n0, int ordering) {
+// to a plan of the first n0 poses, the structure appended in place and the plan
+// bound through it as the library does.  After each: the schedule is
+// consistent, every front's below rows sit in its parent at the extend-add
+// map's index, the sizes match the row lists, and the structure holds the exact
+// fill of the plan's own ordering (a fresh analysis on P.perm) and the whole pattern.
+int check_append(const TestGraph& G, int n_all, int n0, int ordering) {
+  auto upto = [&](int lo, int hi) {   // the factors whose later pose is in [lo, hi)
+    TestGraph g;
+    for (const int2& f : G.e)
+      if (std::max(f.x, f.y) >= lo && std::max(f.x, f.y) < hi) g.add(f.x, f.y);
+    g.n = hi;
+    return g;
+  };
+  TestGraph B = upto(0, n0);
+  pgo::GraphStructure S = built(B);
   pgo::CholPlan P;
   P.ordering = ordering;
-  const Pattern B = restrict_pattern(G, n0);
-  pgo::chol_analyze(P, n0, B.row_ptr, B.col);
-  emulate_bind(P, B.row_ptr, B.col, G.n);
+  pgo::chol_analyze(P, n0, S.row_ptr, S.slot_col);
+  S.bind(P.iperm);
+  remap_sources(P, S);
   {   // the growth limit applies to the plan after the append: no headroom refuses the first one
     pgo::CholPlan Q;
     Q.ordering = ordering;
-    pgo::chol_analyze(Q, n0, B.row_ptr, B.col);
-    const Pattern G1 = restrict_pattern(G, n0 + 1);
+    pgo::chol_analyze(Q, n0, S.row_ptr, S.slot_col);
+    TestGraph B1 = upto(0, n0 + 1);
+    const pgo::GraphStructure S1 = built(B1);
     std::vector<int2> pairs;
-    for (int k = G1.row_ptr[n0]; k < G1.row_ptr[n0 + 1]; k++) pairs.push_back(make_int2(n0, G1.col[k]));
-    if (pgo::chol_append(Q, n0 + 1, G1.row_ptr, G1.col, pairs, 1 << 30, 1.0)) return fail("append: growth limit not applied");
+    for (int k = S1.row_ptr[n0]; k < S1.row_ptr[n0 + 1]; k++) pairs.push_back(make_int2(n0, S1.slot_col[k]));
+    if (pgo::chol_append(Q, n0 + 1, S1.row_ptr, S1.slot_col, pairs, 1 << 30, 1.0)) return fail("append: growth limit not applied");
     if (Q.n != n0) return fail("append: a refused append changed the plan");
   }
-  for (int n = n0 + 1; n <= G.n; n++) {
-    const Pattern Gn = restrict_pattern(G, n);
+  for (int n = n0 + 1; n <= n_all; n++) {
+    const TestGraph add = upto(n - 1, n);
+    for (const int2& f : add.e) B.add(f.x, f.y);
+    B.n = n;
+    pgo::StructureDelta dl;
+    if (!S.append(n, add.e, B.eom.data(), true, &dl)) return fail("append: the structure refused a new pose");
     std::vector<int2> pairs;
-    for (int k = Gn.row_ptr[n - 1]; k < Gn.row_ptr[n]; k++) pairs.push_back(make_int2(n - 1, Gn.col[k]));
-    if (!pgo::chol_append(P, n, Gn.row_ptr, Gn.col, pairs, 1 << 30, 1e30)) return fail("append: refused");
+    for (int k = S.row_ptr[n - 1]; k < S.row_ptr[n]; k++) pairs.push_back(make_int2(n - 1, S.slot_col[k]));
+    if (!pgo::chol_append(P, n, S.row_ptr, S.slot_col, pairs, 1 << 30, 1e30)) return fail("append: refused");
     if (P.schedule_error) return fail("append: panel schedule bookkeeping");
-    if (check_assembly(P) || check_first_writes(P) || check_sources(P, Gn.row_ptr, Gn.col, G.n) || check_splice(P, Gn.row_ptr, Gn.col, G.n)) return 1;
-    emulate_bind(P, Gn.row_ptr, Gn.col, G.n);   // (the next append splices)
-    if (P.n != n || !pgo::chol_covers(P, n, Gn.row_ptr, Gn.col)) return fail("append: pattern not covered");
+    if (check_assembly(P) || check_first_writes(P) || check_sources(P, S.row_ptr, S.slot_col, &S)) return 1;
+    S.bind(P.iperm);   // (the old poses keep their order: the new slots only)
+    if (check_splice(P, S)) return 1;
+    remap_sources(P, S);   // (the next append splices)
+    if (check_sources(P, S.row_ptr, S.slot_col, &S)) return 1;
+    if (P.n != n || !pgo::chol_covers(P, n, S.row_ptr, S.slot_col)) return fail("append: pattern not covered");
     for (int s = 0; s < P.ns; s++) {
       const int wp = P.sfirst[s + 1] - P.sfirst[s], nr = P.rptr[s + 1] - P.rptr[s];
       if (P.m[s] != 3 * nr || P.w[s] != 3 * wp || P.ea_ptr[s + 1] - P.ea_ptr[s] != nr - wp)
@@ -405,7 +457,7 @@ int check_append(const Pattern& G, int n0, int ordering) {
     }
     pgo::CholPlan Q;
     Q.order_in = P.perm;
-    pgo::chol_analyze(Q, n, Gn.row_ptr, Gn.col);
+    pgo::chol_analyze(Q, n, S.row_ptr, S.slot_col);
     for (int q = 0; q < Q.ns; q++)
       for (int a = Q.rptr[q]; a < Q.rptr[q + 1]; a++)
         for (int j = Q.sfirst[q]; j < Q.sfirst[q + 1]; j++) {
@@ -416,13 +468,265 @@ int check_append(const Pattern& G, int n0, int ordering) {
           }
         }
   }
-  std::printf("append: %d poses onto %d, %d fronts, flops %.3g\n", G.n - n0, n0, P.ns, P.flops);
+  {   // the structure after ten in-place appends and incremental binds: a rebuild, bound whole
+    pgo::GraphStructure F = built(B);
+    F.bind(P.iperm);
+    if (S.codes() != F.codes() || S.eside() != F.eside() || S.row_ptr != F.row_ptr || S.slot_col != F.slot_col)
+      return fail("append: the structure differs from a rebuild");
+  }
+  std::printf("append: %d poses onto %d, %d fronts, flops %.3g\n", n_all - n0, n0, P.ns, P.flops);
+  return 0;
+}
+
+// What the device holds: the uploader's copies replayed on host arrays (the
+// ranges pgo_api.cpp copies after build / append / bind / unbind, nothing more).
+struct DeviceCopy {
+  std::vector<int2> eij;
+  std::vector<int> prior_ptr, row_ptr, code, col, erow, s1_ptr, s1pos, s1fac, brow;
+  std::vector<unsigned char> eside;
+  std::vector<double> Dc;
+  template <class T>
+  static void put(std::vector<T>& dst, const std::vector<T>& src, size_t first, size_t end) {
+    if (dst.size() < src.size()) dst.resize(src.size());
+    std::copy(src.begin() + first, src.begin() + end, dst.begin() + first);
+  }
+  void upload(const pgo::GraphStructure& S) {
+    eij = S.eij, prior_ptr = S.prior_ptr, row_ptr = S.row_ptr, code = S.codes(), col = S.slot_col;
+    erow = S.erow, s1_ptr = S.s1_ptr, s1pos = S.s1pos, s1fac = S.s1fac, brow = S.brow, Dc = S.Dc;
+  }
+  void append(const pgo::GraphStructure& S, const pgo::StructureDelta& d) {
+    const size_t n = S.n, ne = S.ne();
+    put(eij, S.eij, d.ne_old, ne);
+    put(prior_ptr, S.prior_ptr, d.n_old + 1, n + 1);
+    put(row_ptr, S.row_ptr, d.r0 + 1, n + 1);
+    put(code, S.codes(), d.k0, 2 * ne);
+    put(col, S.slot_col, d.k0, 2 * ne);
+    put(erow, S.erow, d.x0 + 1, n + 1);
+    put(s1_ptr, S.s1_ptr, d.y0 + 1, n + 1);
+    s1pos = S.s1pos, s1fac = S.s1fac, brow = S.brow;
+    for (int y : d.dc_rows) put(Dc, S.Dc, 6 * (size_t)y, 6 * (size_t)y + 6);
+    put(Dc, S.Dc, 6 * (size_t)d.n_old, 6 * n);
+  }
+  void bind(const pgo::GraphStructure& S, pgo::SlotRange r) {
+    put(code, S.codes(), r.begin, r.end);
+    eside = S.eside();
+  }
+};
+
+template <class T>
+bool same_bits(const std::vector<T>& a, const std::vector<T>& b) {
+  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
+
+// S (appended in place) and D (the device after the delta's copies) against F,
+// a fresh build of the grown graph: array for array, Dc bitwise; the owner bits apart
+int same_structure(pgo::GraphStructure& S, const DeviceCopy& D, pgo::GraphStructure& F) {
+  if (S.n != F.n || !same_bits(S.eij, F.eij) || S.dorder != F.dorder || S.pv != F.pv || S.prior_ptr != F.prior_ptr ||
+      S.porder != F.porder || S.row_ptr != F.row_ptr || S.slot_col != F.slot_col || S.edge_slot0 != F.edge_slot0 ||
+      S.erow != F.erow || S.s1_ptr != F.s1_ptr || S.s1pos != F.s1pos || S.s1fac != F.s1fac || S.brow != F.brow ||
+      !same_bits(S.Dc, F.Dc) || S.G != F.G || S.G1 != F.G1 || S.gauge_free != F.gauge_free)
+    return fail("structure: an in-place append differs from a rebuild");
+  for (size_t k = 0; k < S.codes().size(); k++)
+    if ((S.codes()[k] | 2) != (F.codes()[k] | 2)) return fail("structure: slot codes differ from a rebuild");
+  for (int v = 1; v < S.n; v++)
+    if (S.same_component(0, v) != F.same_component(0, v) || S.same_component(v - 1, v) != F.same_component(v - 1, v))
+      return fail("structure: components differ from a rebuild");
+  if (!same_bits(D.eij, F.eij) || D.prior_ptr != F.prior_ptr || D.row_ptr != F.row_ptr || D.col != F.slot_col ||
+      D.erow != F.erow || D.s1_ptr != F.s1_ptr || D.s1pos != F.s1pos || D.s1fac != F.s1fac || D.brow != F.brow ||
+      !same_bits(D.Dc, F.Dc) || D.code != S.codes())
+    return fail("structure: the append's delta does not cover what changed");
+  return 0;
+}
+
+// owner slots of every factor in `code` (device factor -> count, side of the last)
+bool one_owner_each(const std::vector<int>& code, int ne, std::vector<unsigned char>* side = nullptr) {
+  std::vector<int> cnt(ne, 0);
+  if (side) side->assign(ne, 0);
+  for (int c : code)
+    if (c & 2) {
+      cnt[c >> 2]++;
+      if (side) (*side)[c >> 2] = (unsigned char)(c & 1);
+    }
+  return std::all_of(cnt.begin(), cnt.end(), [](int c) { return c == 1; });
+}
+
+// a chain of 48 poses, 10 closures (none from the last pose), 4 of them twice
+// (parallel factors, apart in user order); optionally a second component of 8
+// poses and a prior on pose 0
+TestGraph small_graph(bool prior, bool second_component) {
+  TestGraph g = make_edges(47, 10, 11, 0);
+  g.add(47 - 1, 47);
+  g.n = 48;
+  for (int q = 0; q < 10; q += 3) g.add(g.e[46 + q].x, g.e[46 + q].y);
+  if (second_component) {
+    for (int i = 48; i + 1 < 56; i++) g.add(i, i + 1);
+    g.n = 56;
+  }
+  if (prior) g.pv.push_back(0);
+  return g;
+}
+
+// the append shapes; k counts the applications to one graph
+enum { kPoseToRow0, kMiddleRow, kParallel, kThreePoses, kJoin, kShapes };
+TestGraph append_shape(int kind, const pgo::GraphStructure& S, int k) {
+  const int n = S.n;
+  TestGraph a;
+  a.n = n;
+  switch (kind) {
+    case kPoseToRow0: a.n = n + 1, a.add(n - 1, n), a.add(n, 0); break;
+    case kMiddleRow: a.add(n - 1, 20 + k); break;
+    case kParallel: a.add(S.eij.back().x, S.eij.back().y); break;
+    case kThreePoses: a.n = n + 3, a.add(n - 1, n), a.add(n, n + 1), a.add(n + 1, n + 2), a.add(n + 2, 7 + k); break;
+    case kJoin: a.n = n + 1, a.add(n - 1, n), a.add(n, 5 + k); break;   // (n - 1: the second component's end)
+  }
+  return a;
+}
+
+// One shape applied `reps` times in a row.  Pre-plan: every result equals a
+// rebuild, codes included.  Bound first (random order `seed`): no bind between
+// the appends (the second meets the first's new-slot list), each leaves the old
+// slots' bits and one owner slot per factor on the device unless kMixed, then
+// the incremental bind equals a full bind of a rebuild under the same order,
+// unbind gives the rebuild's pre-plan codes, a changed order binds whole.
+int check_shape(const TestGraph& g0, int kind, int reps, bool bound, unsigned seed) {
+  TestGraph g = g0;
+  pgo::GraphStructure S = built(g);
+  DeviceCopy D;
+  D.upload(S);
+  std::mt19937 rng(seed);
+  std::vector<int> iperm(g.n);
+  for (int i = 0; i < g.n; i++) iperm[i] = i;
+  std::shuffle(iperm.begin(), iperm.end(), rng);
+  if (bound) {
+    const pgo::SlotRange r = S.bind(iperm);
+    if (r.begin != 0 || r.end != S.nslots() || S.slot_codes() != pgo::GraphStructure::kBound || S.bind_row0() != S.n)
+      return fail("owner bits: the first bind's range");
+    D.bind(S, r);
+    std::vector<unsigned char> side;
+    if (!one_owner_each(D.code, S.ne(), &side) || side != D.eside) return fail("owner bits: bind after a build");
+    for (int r2 = 0; r2 < S.n; r2++)
+      for (int k = S.row_ptr[r2]; k < S.row_ptr[r2 + 1]; k++)
+        if (((D.code[k] & 2) != 0) != (iperm[r2] > iperm[S.slot_col[k]])) return fail("owner bits: not the lower triangle");
+  }
+  int k0_min = S.nslots();
+  for (int k = 0; k < reps; k++) {
+    const TestGraph a = append_shape(kind, S, k);
+    const std::vector<int> before = D.code;
+    const int n_old = S.n, ne_old = S.ne();
+    for (const int2& f : a.e) g.add(f.x, f.y);
+    g.n = a.n;
+    pgo::StructureDelta dl;
+    if (!S.append(g.n, a.e, g.eom.data(), true, &dl)) return fail("structure: an append in device order refused");
+    D.append(S, dl);
+    pgo::GraphStructure F = built(g);
+    if (same_structure(S, D, F)) return 1;
+    if (dl.n_old != n_old || dl.ne_old != ne_old || dl.k0 != S.row_ptr[dl.r0] || (kind == kPoseToRow0 && dl.r0 != 0) ||
+        (kind == kMiddleRow && dl.r0 != 20 + k))
+      return fail("structure: the append's delta");
+    k0_min = std::min(k0_min, dl.k0);
+    if (!bound) {
+      if (S.codes() != F.codes() || S.slot_codes() != pgo::GraphStructure::kPrePlan) return fail("structure: pre-plan codes");
+      continue;
+    }
+    if (S.slot_codes() != (k0_min > 0 ? pgo::GraphStructure::kMixed : pgo::GraphStructure::kBound) || S.bind_row0() > dl.r0)
+      return fail("owner bits: the state after an append");
+    if (k == 0) {   // every old slot bound, still (the merge keeps them, in order), the new ones pre-plan
+      size_t o = 0;
+      for (size_t q = 0; q < D.code.size(); q++) {
+        if ((D.code[q] >> 2) < ne_old ? (o >= before.size() || D.code[q] != before[o++]) : D.code[q] != F.codes()[q])
+          return fail("owner bits: an append moved or changed a bound slot");
+      }
+      if (o != before.size() || !one_owner_each(D.code, S.ne())) return fail("owner bits: per factor after an append");
+    } else {   // the first append's list is stale: pre-plan codes from the first changed slot on
+      if (!std::equal(D.code.begin() + dl.k0, D.code.end(), F.codes().begin() + dl.k0))
+        return fail("owner bits: a second append before a bind left bound codes in its tail");
+    }
+  }
+  if (kind == kJoin && (g0.pv.empty() ? !S.gauge_free : S.gauge_free)) return fail("structure: gauge after joining components");
+  if (!bound) return 0;
+  for (int v = (int)iperm.size(); v < g.n; v++) iperm.push_back(v);
+  pgo::GraphStructure F = built(g);
+  {   // append -> unbind on a copy: the rebuild's pre-plan codes, whole
+    pgo::GraphStructure U = S;
+    DeviceCopy DU = D;
+    const bool up = U.unbind();
+    if (up != (k0_min > 0)) return fail("owner bits: unbind without mixed codes, or none with them");
+    if (up) DU.code = U.codes();
+    if (!one_owner_each(DU.code, U.ne()) || (up && (DU.code != F.codes() || U.slot_codes() != pgo::GraphStructure::kPrePlan)))
+      return fail("owner bits: unbind after an append");
+  }
+  const pgo::SlotRange r = S.bind(iperm);
+  if (r.begin != k0_min || r.end != S.nslots()) return fail("owner bits: the incremental bind's range");
+  D.bind(S, r);
+  F.bind(iperm);
+  if (S.codes() != F.codes() || D.code != F.codes() || S.eside() != F.eside())
+    return fail("owner bits: an incremental bind differs from a full bind of a rebuild");
+  std::shuffle(iperm.begin(), iperm.end(), rng);
+  S.order_changed();
+  const pgo::SlotRange r2 = S.bind(iperm);
+  D.bind(S, r2);
+  pgo::GraphStructure F2 = built(g);
+  F2.bind(iperm);
+  if (r2.begin != 0 || D.code != F2.codes() || S.eside() != F2.eside()) return fail("owner bits: bind after a changed order");
+  return 0;
+}
+
+int check_structure() {
+  const TestGraph base = small_graph(true, false);
+  for (int kind = 0; kind < kJoin; kind++)
+    for (int reps : {1, 2})
+      for (bool bound : {false, true})
+        if (check_shape(base, kind, reps, bound, 100 + kind)) return 1;
+  for (bool prior : {false, true})   // a second component joined: anchored by the prior, or gauge-free still
+    for (bool bound : {false, true})
+      if (check_shape(small_graph(prior, true), kJoin, 2, bound, 7)) return 1;
+  {   // refusals leave the structure untouched
+    pgo::GraphStructure S = built(base), F = built(base);
+    S.bind(std::vector<int>(base.n, 0)), F.bind(std::vector<int>(base.n, 0));
+    DeviceCopy D;
+    D.upload(S);
+    TestGraph g = base;
+    g.add(3, 30);   // sorts before (46, 47)
+    pgo::StructureDelta dl;
+    if (S.append(g.n, {g.e.back()}, g.eom.data(), true, &dl)) return fail("structure: a factor before the last old one appended");
+    if (S.append(base.n, {}, base.eom.data(), true, &dl)) return fail("structure: nothing new appended");
+    if (S.append(base.n - 1, {}, base.eom.data(), true, &dl)) return fail("structure: a shrunk graph appended");
+    if (same_structure(S, D, F) || S.codes() != F.codes() || S.bind_row0() != F.bind_row0() || S.slot_codes() != F.slot_codes())
+      return fail("structure: a refused append changed the structure");
+    TestGraph v;   // vertices only: no factor to sort after
+    v.n = 3;
+    pgo::GraphStructure E = built(v);
+    v.add(0, 1);
+    if (E.append(3, v.e, v.eom.data(), true, &dl) || E.n != 3 || E.ne() != 0 || E.row_ptr != std::vector<int>(4, 0))
+      return fail("structure: an append onto no factors");
+  }
+  {   // packing: (x, y, theta) -> (x, y, cos, sin), six doubles -> three double2, through `order`
+    const double pi = 3.14159265358979323846;
+    const double z[] = {1.5, -2.25, pi, 0.0, 1e-300, -pi, -7.0, 3.0, 0.3, 4.0, 5.0, -0.0};
+    double om[24];
+    for (int q = 0; q < 24; q++) om[q] = 0.5 + q * 1.25;
+    const int order[] = {2, 0, 3, 1};
+    double4 hz[4];
+    double2 hom[12];
+    pgo::pack_measurements(z, om, order, 4, hz, hom);
+    for (int k = 0; k < 4; k++) {
+      const int e = order[k];
+      const double th = z[3 * e + 2];
+      const double want[4] = {z[3 * e], z[3 * e + 1], std::cos(th), std::sin(th)};
+      const double got[4] = {hz[k].x, hz[k].y, hz[k].z, hz[k].w};
+      if (std::memcmp(want, got, sizeof(want))) return fail("packing: a measurement");
+      for (int q = 0; q < 3; q++)
+        if (hom[3 * k + q].x != om[6 * e + 2 * q] || hom[3 * k + q].y != om[6 * e + 2 * q + 1]) return fail("packing: information");
+    }
+  }
+  std::printf("structure module: append shapes, refusals, owner bits, packing ok\n");
   return 0;
 }
 
 }  // namespace
 
 int main() {
+  if (check_structure()) return 1;
   for (int n : {1, 2, 5}) {   // graphs smaller than the planner's thread count
     const Pattern G = restrict_pattern(make_pattern(40, 0, 3), n);
     pgo::CholPlan P;
@@ -472,7 +776,7 @@ int main() {
     pgo::chol_analyze(R, G3.n, G3.row_ptr, G3.col);
     if (!pgo::chol_covers(R, G3.n, G3.row_ptr, G3.col) || R.schedule_error) return fail("given ordering");
     // appended poses: the incremental symbolic update
-    if (check_append(make_pattern(1500, 200, 9, {}, 40), 1490, ordering)) return 1;
+    if (check_append(make_edges(1500, 200, 9, 40), 1500, 1490, ordering)) return 1;
   }
   {   // a 2-D grid of poses: nested dissection gives big separator fronts (many
       // panels, kKB block boundaries, partial last panels) -- the look-ahead

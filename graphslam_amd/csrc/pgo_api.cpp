@@ -26,6 +26,7 @@
 #include "pgo_comm.h"
 #include "pgo_search.h"
 #include "pgo_device.h"
+#include "pgo_structure.h"
 
 using pgo::DevGraph;
 
@@ -45,16 +46,6 @@ struct Staging {
   char* buf = nullptr;
   size_t cap = 0, used = 0;
   hipEvent_t done = nullptr;                // recorded after a batch's copies (stage_end)
-};
-
-struct HostStructure {
-  std::vector<int2> eij;           // device order
-  std::vector<int> dorder;         // device factor -> user factor index
-  std::vector<int> pv, row_ptr, slot_edge, slot_col, prior_ptr, porder;
-  std::vector<int> uf;             // union-find parents over the vertices (gauge check)
-  std::vector<int> erow, s1_ptr, s1pos;   // the Cholesky-mode sweep structure (upload_structure)
-  std::vector<int> spare_rp, spare_sc, spare_se;   // the previous block-CSR arrays, reused by the next append
-  bool gauge_free = false;
 };
 
 struct pgo_graph {
@@ -78,27 +69,6 @@ struct pgo_graph {
   bool dev_values = false;                  // device pose == host xyt
   bool host_values = true;                  // host xyt == device pose
   DevGraph d;
-  std::vector<int> edge_slot0;              // side-0 slot of every between factor (user order)
-  std::vector<int> h_slot_edge;             // host copy of slot_edge (owner bits)
-  // the device slot_edge carries the Cholesky plan's owner bits (bind_plan);
-  // after an in-place append its rows from the first changed one carry the
-  // pre-plan codes instead (side 0 owns), so the two halves disagree until the
-  // next bind_plan -- the PCG path (k_model_decrease counts `se & 2` slots)
-  // re-uploads the whole array first (slot_codes_mixed)
-  bool slot_codes_plan = false;
-  bool slot_codes_mixed = false;
-  // rows from bind_row0 on need their owner bits (re)computed by the next
-  // bind_plan (in-place appends: the plan keeps the old poses' order, so the
-  // earlier rows' bits and their factors' owner sides stand); h_eside the
-  // owner side of every factor, as uploaded
-  int bind_row0 = 0;
-  std::vector<unsigned char> h_eside;
-  // mirror_bound: h_slot_edge (and the device copy) carries the plan's owner
-  // bits on every slot but new_slots (an append's, pre-plan codes): the next
-  // bind_plan on the same order sets only those
-  bool mirror_bound = false;
-  std::vector<int> new_slots;
-  bool gauge_free = false;                 // some connected component has no prior
   double* h_scal = nullptr;                 // pinned
   int* h_ctrl = nullptr;                    // pinned
   hipEvent_t ev[6] = {};
@@ -106,7 +76,6 @@ struct pgo_graph {
   hipEvent_t pev[2 * kProfPairs] = {};
   int pk_iter[kProfPairs] = {};
   // ---- supernodal Cholesky (built on first use; structure-dependent) ----
-  std::vector<int> h_row_ptr, h_slot_col;   // block-CSR pattern (old indices)
   pgo::CholPlan chol;
   int ordering = pgo::kOrderNd;             // fill-reducing ordering (pgo_opts.ordering)
   int part_size = 1;                        // subtree partition the plan must have (PGO_MULTI_PARTITION)
@@ -159,10 +128,9 @@ struct pgo_graph {
   hipEvent_t lin_done = nullptr;            // linearisation complete
   int lane_cap = 8;                         // 1 after a lane allocation failed (reset per plan)
   // ---- incremental appends (append_structure, the live re-solve) ----
-  HostStructure hs;                         // the structure the device holds (host side)
-  std::vector<double> h_Dc;                 // its per-row sums of side-1 Omega
+  pgo::GraphStructure gs;                   // the structure the device holds, host side (pgo_structure.h)
   size_t cap_n = 0, cap_ne = 0;             // device capacities in vertices / factors
-  bool dev_complete = false;                // the device holds hs exactly (appendable)
+  bool dev_complete = false;                // the device holds gs exactly (appendable)
   int last_upload = 0;                      // 1 full upload, 2 append (diagnostics)
   bool saved_valid = false;                 // d.pose_saved holds a snapshot of this structure (pgo_save_values)
   // ---- closest-keyframe search scratch ----
@@ -416,25 +384,39 @@ int download_values(pgo_graph* g) {
   return PGO_OK;
 }
 
-// Build the device graph: resolve keys (GTSAM raises ValuesKeyDoesNotExist at
-// optimize time for a factor on an unknown key), block-CSR slots, priors.
-// Host-side structure of the graph (no HIP): resolved factor endpoints,
-// block-CSR slots, priors by vertex, gauge freedom.
-
-int build_structure(pgo_graph* g, HostStructure& H) {
-  const int n = (int)g->keys.size();
-  const int ne = (int)g->ek1.size();
-  const int np = (int)g->pk.size();
-  std::vector<int2> eij(ne);
-  for (int e = 0; e < ne; e++) {
+// Factors [first, ne) resolved to vertex indices (GTSAM raises
+// ValuesKeyDoesNotExist at optimize time for a factor on an unknown key).
+int resolve_edges(pgo_graph* g, size_t first, std::vector<int2>& eij) {
+  const size_t ne = g->ek1.size();
+  eij.resize(ne - first);
+  for (size_t e = first; e < ne; e++) {
     auto a = g->index.find(g->ek1[e]), b = g->index.find(g->ek2[e]);
     if (a == g->index.end() || b == g->index.end()) {
       const uint64_t k = a == g->index.end() ? g->ek1[e] : g->ek2[e];
       return fail(g, PGO_E_NO_KEY, "between factor " + std::to_string(e) + " references key " +
                                        std::to_string(k) + " with no inserted value");
     }
-    eij[e] = make_int2(a->second, b->second);
+    eij[e - first] = make_int2(a->second, b->second);
   }
+  return PGO_OK;
+}
+
+// loss kind and parameter of `count` factors, out k from user factor order[k]
+void gather_losses(const pgo_graph* g, const int* order, size_t count, std::vector<unsigned char>& hl,
+                   std::vector<double>& hk) {
+  hl.resize(count);
+  hk.resize(count);
+  for (size_t k = 0; k < count; k++) {
+    hl[k] = g->eloss[order[k]];
+    hk[k] = g->ek[order[k]];
+  }
+}
+
+// The host structure of the whole graph (pgo_structure.h), keys resolved.
+int build_structure(pgo_graph* g, pgo::GraphStructure& S) {
+  const int np = (int)g->pk.size();
+  std::vector<int2> eij_user;
+  RC_TRY(resolve_edges(g, 0, eij_user));
   std::vector<int> pv(np);
   for (int q = 0; q < np; q++) {
     auto a = g->index.find(g->pk[q]);
@@ -442,133 +424,21 @@ int build_structure(pgo_graph* g, HostStructure& H) {
       return fail(g, PGO_E_NO_KEY, "prior factor on key " + std::to_string(g->pk[q]) + " with no inserted value");
     pv[q] = a->second;
   }
-  // device order of the factors: sorted by (ei, ej), so that the side-0 slots
-  // of a row read consecutive factors (coalesced factor loads in k_linearize)
-  std::vector<int> dorder(ne);
-  for (int e = 0; e < ne; e++) dorder[e] = e;
-  std::stable_sort(dorder.begin(), dorder.end(), [&](int a, int b) {
-    return eij[a].x != eij[b].x ? eij[a].x < eij[b].x : eij[a].y < eij[b].y;
-  });
-  {
-    std::vector<int2> t(ne);
-    for (int e = 0; e < ne; e++) t[e] = eij[dorder[e]];
-    eij.swap(t);
-  }
-  // block-CSR rows: every factor owns a slot in row ei (side 0) and row ej (side 1)
-  const int ns = 2 * ne;
-  std::vector<int> row_ptr(n + 1, 0);
-  for (int e = 0; e < ne; e++) {
-    row_ptr[eij[e].x + 1]++;
-    row_ptr[eij[e].y + 1]++;
-  }
-  for (int i = 0; i < n; i++) row_ptr[i + 1] += row_ptr[i];
-  std::vector<int> fillp(row_ptr.begin(), row_ptr.end() - 1);
-  std::vector<int> slot_edge(ns), slot_col(ns);
-  for (int e = 0; e < ne; e++) {   // owner: side 0 until a Cholesky plan re-assigns it
-    int s0 = fillp[eij[e].x]++;
-    slot_edge[s0] = (e << 2) | 2;
-    slot_col[s0] = eij[e].y;
-    int s1 = fillp[eij[e].y]++;
-    slot_edge[s1] = (e << 2) | 1;
-    slot_col[s1] = eij[e].x;
-  }
-  // order each row by column (locality of the x gathers)
-  std::vector<std::pair<int, int>> tmp;
-  for (int i = 0; i < n; i++) {
-    const int b = row_ptr[i], en = row_ptr[i + 1];
-    if (en - b < 2) continue;
-    tmp.clear();
-    for (int k = b; k < en; k++) tmp.emplace_back(slot_col[k], slot_edge[k]);
-    std::sort(tmp.begin(), tmp.end());
-    for (int k = b; k < en; k++) {
-      slot_col[k] = tmp[k - b].first;
-      slot_edge[k] = tmp[k - b].second;
-    }
-  }
-  // connected components without a prior leave H singular (3-dof gauge):
-  // GTSAM's Cholesky throws IndeterminantLinearSystemException there (GN);
-  // LM's damping keeps it solvable.
-  {
-    std::vector<int>& uf = H.uf;
-    uf.resize(n);
-    for (int i = 0; i < n; i++) uf[i] = i;
-    auto find = [&](int x) {
-      while (uf[x] != x) x = uf[x] = uf[uf[x]];
-      return x;
-    };
-    for (int e = 0; e < ne; e++) {
-      const int a = find(eij[e].x), b = find(eij[e].y);
-      if (a != b) uf[a] = b;
-    }
-    std::vector<char> anchored(n, 0);
-    for (int q = 0; q < np; q++) anchored[find(pv[q])] = 1;
-    g->gauge_free = false;
-    for (int i = 0; i < n; i++)
-      if (!anchored[find(i)]) g->gauge_free = true;
-  }
-  // priors CSR by vertex
-  std::vector<int> prior_ptr(n + 1, 0);
-  for (int q = 0; q < np; q++) prior_ptr[pv[q] + 1]++;
-  for (int i = 0; i < n; i++) prior_ptr[i + 1] += prior_ptr[i];
-  std::vector<int> porder(np);
-  {
-    std::vector<int> f(prior_ptr.begin(), prior_ptr.end() - 1);
-    for (int q = 0; q < np; q++) porder[f[pv[q]]++] = q;
-  }
-  H.gauge_free = g->gauge_free;
-  H.dorder = std::move(dorder);
-  H.eij = std::move(eij);
-  H.pv = std::move(pv);
-  H.row_ptr = std::move(row_ptr);
-  H.slot_edge = std::move(slot_edge);
-  H.slot_col = std::move(slot_col);
-  H.prior_ptr = std::move(prior_ptr);
-  H.porder = std::move(porder);
+  S.build((int)g->keys.size(), eij_user, std::move(pv), g->eom.data(), g->n_robust > 0);
   return PGO_OK;
 }
 
+// Build the device graph: the host structure, allocate with room for appends, copy.
 int upload_structure(pgo_graph* g) {
   RC_TRY(ensure_hip(g));
   RC_TRY(download_values(g));
-  HostStructure H;
-  RC_TRY(build_structure(g, H));
-  const int n = (int)g->keys.size();
-  const int ne = (int)g->ek1.size();
-  const int np = (int)g->pk.size();
-  const int ns = 2 * ne;
-  const auto& eij = H.eij;
-  const auto& pv = H.pv;
-  const auto& row_ptr = H.row_ptr;
-  const auto& slot_edge = H.slot_edge;
-  const auto& slot_col = H.slot_col;
-  const auto& prior_ptr = H.prior_ptr;
-  const auto& porder = H.porder;
-  g->h_row_ptr = row_ptr;
-  g->h_slot_col = slot_col;
-  g->h_slot_edge = slot_edge;
-  g->edge_slot0.assign(ne, -1);   // user factor -> its side-0 slot
-  for (int k = 0; k < ns; k++)
-    if ((slot_edge[k] & 1) == 0) g->edge_slot0[H.dorder[slot_edge[k] >> 2]] = k;
+  pgo::GraphStructure& S = g->gs;
+  RC_TRY(build_structure(g, S));
+  const int n = S.n, ne = S.ne(), np = (int)S.pv.size(), ns = 2 * ne;
   std::vector<double4> hz(ne), hpz(np);
   std::vector<double2> hom(3 * (size_t)ne), hpom(3 * (size_t)np);
-  for (int de = 0; de < ne; de++) {
-    const int e = H.dorder[de];
-    const double th = g->ez[3 * e + 2];
-    hz[de] = make_double4(g->ez[3 * e], g->ez[3 * e + 1], std::cos(th), std::sin(th));
-    const double* o = &g->eom[6 * (size_t)e];
-    hom[3 * de] = make_double2(o[0], o[1]);
-    hom[3 * de + 1] = make_double2(o[2], o[3]);
-    hom[3 * de + 2] = make_double2(o[4], o[5]);
-  }
-  for (int t = 0; t < np; t++) {
-    const int q = porder[t];
-    const double th = g->pz[3 * q + 2];
-    hpz[t] = make_double4(g->pz[3 * q], g->pz[3 * q + 1], std::cos(th), std::sin(th));
-    const double* o = &g->pom[6 * (size_t)q];
-    hpom[3 * t] = make_double2(o[0], o[1]);
-    hpom[3 * t + 1] = make_double2(o[2], o[3]);
-    hpom[3 * t + 2] = make_double2(o[4], o[5]);
-  }
+  pgo::pack_measurements(g->ez.data(), g->eom.data(), S.dorder.data(), ne, hz.data(), hom.data());
+  pgo::pack_measurements(g->pz.data(), g->pom.data(), S.porder.data(), np, hpz.data(), hpom.data());
   // the values already resident stay bit for bit (no host atan2 -> cos / sin
   // round trip): vertices are append-only, so the first n_old keep their index
   // (freed on every exit path: an early error return below must not leak it)
@@ -607,71 +477,30 @@ int upload_structure(pgo_graph* g) {
       g->stage.cap = want;
     }
   }
-  // lanes per row: smallest power of two >= mean degree, in [4, 32]
-  const double mean_deg = n ? (double)ns / n : 0.0;
-  d.G = 4;
-  while (d.G < 32 && d.G < mean_deg) d.G *= 2;
-  d.G1 = 4;
-  while (d.G1 < 32 && d.G1 < (n ? (double)ne / n : 0.0)) d.G1 *= 2;
-  // Cholesky-mode sweep structure: factors are sorted by (ei, ej), so the
-  // side-0 factors of row i are the contiguous range [erow[i], erow[i+1]);
-  // side-1 factors of row j take positions s1_ptr[j].. in device order (s1pos).  Dc[j] is
-  // the (iteration-invariant) sum of Omega over row j's side-1 factors.
-  std::vector<int> erow(n + 1, 0), s1_ptr(n + 1, 0), s1pos(ne);
-  std::vector<double> Dc(6 * (size_t)n, 0.0);
-  for (int e = 0; e < ne; e++) {
-    erow[eij[e].x + 1]++;
-    s1_ptr[eij[e].y + 1]++;
-  }
-  for (int i = 0; i < n; i++) {
-    erow[i + 1] += erow[i];
-    s1_ptr[i + 1] += s1_ptr[i];
-  }
-  {
-    std::vector<int> f(s1_ptr.begin(), s1_ptr.end() - 1);
-    for (int e = 0; e < ne; e++) {
-      const int j = eij[e].y;
-      s1pos[e] = f[j]++;
-      const double* o = &g->eom[6 * (size_t)H.dorder[e]];
-      for (int q = 0; q < 6; q++) Dc[6 * (size_t)j + q] += o[q];
-    }
-  }
-  // k_linearize_own blocks: whole rows, greedily packed to <= kThreads side-0
-  // factors and <= kThreads rows (a row with more factors is a block alone)
-  std::vector<int> brow(1, 0);
-  for (int r = 0; r < n;) {
-    int r1 = r + 1;
-    while (r1 < n && r1 - r < pgo::kThreads && erow[r1 + 1] - erow[r] <= pgo::kThreads) r1++;
-    brow.push_back(r1);
-    r = r1;
-  }
-  d.nlb = (int)brow.size() - 1;
+  d.G = S.G;
+  d.G1 = S.G1;
+  d.nlb = (int)S.brow.size() - 1;
   RC_TRY(dev_alloc(g, &d.brow, cn + 1));
-  RC_TRY(h2d(g, d.brow, brow.data(), brow.size()));
+  RC_TRY(h2d(g, d.brow, S.brow.data(), S.brow.size()));
   RC_TRY(dev_alloc(g, &d.erow, cn + 1));
   RC_TRY(dev_alloc(g, &d.s1_ptr, cn + 1));
   RC_TRY(dev_alloc(g, &d.s1pos, ce));
   RC_TRY(dev_alloc(g, &d.Dc, 6 * cn));
   RC_TRY(dev_alloc(g, &d.W, ce));
-  RC_TRY(h2d(g, d.erow, erow.data(), n + 1));
-  RC_TRY(h2d(g, d.s1_ptr, s1_ptr.data(), n + 1));
-  RC_TRY(h2d(g, d.s1pos, s1pos.data(), ne));
-  RC_TRY(h2d(g, d.Dc, Dc.data(), 6 * (size_t)n));
+  RC_TRY(h2d(g, d.erow, S.erow.data(), n + 1));
+  RC_TRY(h2d(g, d.s1_ptr, S.s1_ptr.data(), n + 1));
+  RC_TRY(h2d(g, d.s1pos, S.s1pos.data(), ne));
+  RC_TRY(h2d(g, d.Dc, S.Dc.data(), 6 * (size_t)n));
   if (g->n_robust > 0) {   // robust losses: kind and k in device order, the side-1 lists' factors
-    std::vector<unsigned char> hl(ne);
-    std::vector<double> hk(ne);
-    std::vector<int> s1fac(ne);
-    for (int e = 0; e < ne; e++) {
-      hl[e] = g->eloss[H.dorder[e]];
-      hk[e] = g->ek[H.dorder[e]];
-      s1fac[s1pos[e]] = e;
-    }
+    std::vector<unsigned char> hl;
+    std::vector<double> hk;
+    gather_losses(g, S.dorder.data(), ne, hl, hk);
     RC_TRY(dev_alloc(g, &d.eloss, ce));
     RC_TRY(dev_alloc(g, &d.ek, ce));
     RC_TRY(dev_alloc(g, &d.s1fac, ce));
     RC_TRY(h2d(g, d.eloss, hl.data(), ne));
     RC_TRY(h2d(g, d.ek, hk.data(), ne));
-    RC_TRY(h2d(g, d.s1fac, s1fac.data(), ne));
+    RC_TRY(h2d(g, d.s1fac, S.s1fac.data(), ne));
     HIP_TRY(g, hipStreamSynchronize(d.stream));   // (the sources are locals)
   }
   RC_TRY(dev_alloc(g, &d.eij, ce));
@@ -699,45 +528,22 @@ int upload_structure(pgo_graph* g) {
   RC_TRY(dev_alloc(g, &d.scal, 16));
   RC_TRY(dev_alloc(g, &d.ctrl, 4));
   std::vector<int> pvs(np);
-  for (int t = 0; t < np; t++) pvs[t] = pv[porder[t]];
-  RC_TRY(h2d(g, d.eij, eij.data(), ne));
+  for (int t = 0; t < np; t++) pvs[t] = S.pv[S.porder[t]];
+  RC_TRY(h2d(g, d.eij, S.eij.data(), ne));
   RC_TRY(h2d(g, d.ez, hz.data(), ne));
   RC_TRY(h2d(g, d.eom, hom.data(), 3 * (size_t)ne));
-  RC_TRY(h2d(g, d.prior_ptr, prior_ptr.data(), n + 1));
+  RC_TRY(h2d(g, d.prior_ptr, S.prior_ptr.data(), n + 1));
   RC_TRY(h2d(g, d.prior_vtx, pvs.data(), np));
   RC_TRY(h2d(g, d.pz, hpz.data(), np));
   RC_TRY(h2d(g, d.pom, hpom.data(), 3 * (size_t)np));
-  RC_TRY(h2d(g, d.row_ptr, row_ptr.data(), n + 1));
-  RC_TRY(h2d(g, d.slot_edge, slot_edge.data(), ns));
-  g->slot_codes_plan = g->slot_codes_mixed = false;   // pre-plan codes throughout
-  g->bind_row0 = 0;
-  g->mirror_bound = false;
-  g->new_slots.clear();
+  RC_TRY(h2d(g, d.row_ptr, S.row_ptr.data(), n + 1));
+  RC_TRY(h2d(g, d.slot_edge, S.codes().data(), ns));   // pre-plan codes throughout
   g->chol.asm_bound = false;   // (a new device factor order: the plan's bound sources are void)
-  RC_TRY(h2d(g, d.slot_col, slot_col.data(), ns));
+  RC_TRY(h2d(g, d.slot_col, S.slot_col.data(), ns));
   HIP_TRY(g, hipMemsetAsync(d.part, 0, sizeof(double) * pgo::kMaxBlocks * pgo::kPartSlices, d.stream));
   HIP_TRY(g, hipStreamSynchronize(d.stream));
   g->dev_structure = true;
-  g->h_Dc = std::move(Dc);
-  H.erow = std::move(erow);
-  H.s1_ptr = std::move(s1_ptr);
-  H.s1pos = std::move(s1pos);
-  {   // room for in-place appends (append_structure), as the device arrays have
-    const size_t rn = g->cap_n + 1, re = g->cap_ne, rs = 2 * g->cap_ne;
-    H.eij.reserve(re);
-    H.dorder.reserve(re);
-    H.erow.reserve(rn);
-    H.s1_ptr.reserve(rn);
-    H.s1pos.reserve(re);
-    H.prior_ptr.reserve(rn);
-    H.uf.reserve(rn);
-    g->edge_slot0.reserve(re);
-    g->h_row_ptr.reserve(rn);
-    g->h_slot_col.reserve(rs);
-    g->h_slot_edge.reserve(rs);
-    g->h_Dc.reserve(6 * rn);
-  }
-  g->hs = std::move(H);
+  S.reserve(g->cap_n, g->cap_ne);   // room for in-place appends (append_structure), as the device arrays have
   g->dev_complete = true;
   g->last_upload = 1;
   if (n_old > 0) {
@@ -747,257 +553,32 @@ int upload_structure(pgo_graph* g) {
   return upload_values(g, n_old);
 }
 
+
 // Appended vertices and between factors (pgo_add_vertex / pgo_add_edge after
 // an upload -- the live re-solve, graph.cpp:180-200) extend the device graph in
 // place when the device holds the previous structure, no prior was added,
-// capacities suffice and the new factors sort after the old ones in device
-// order ((ei, ej): a new keyframe's odometry and loop closures do).  The host
-// structure is updated in step (block-CSR rows merged, side-1 lists, row
-// blocks); only the new factors, the per-row arrays and the slot arrays are
-// uploaded.  Returns 1 when the full upload must run instead.
-// fn(begin, end) over contiguous chunks of [0, n) on the planner's host threads
-// (the live re-solve's per-registration host work; chunk results independent)
-template <class F>
-void host_parallel(int n, F&& fn) {
-  static const int hw = (int)std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
-  const int nth = std::max(1, std::min(hw, n / 16384));
-  pgo::plan_parallel(nth, [&](int t) { fn((int)((long long)n * t / nth), (int)((long long)n * (t + 1) / nth)); });
-}
-
-// PGO_PLAN_TIMING: phase times of the plan / append paths on stderr
-struct PhaseTimer {
-  const char* who;
-  bool on = getenv("PGO_PLAN_TIMING") != nullptr;
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-  explicit PhaseTimer(const char* w) : who(w) {}
-  void operator()(const char* what) {
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "%s %-14s %8.2f ms\n", who, what, std::chrono::duration<double, std::milli>(now - t).count());
-    t = now;
-  }
-};
-
+// capacities suffice and GraphStructure::append takes them (a new keyframe's
+// odometry and loop closures sort after the old factors); only what its delta
+// names is uploaded.  Returns 1 when the full upload must run instead.
 int append_structure(pgo_graph* g) {
-  PhaseTimer phase("append_structure");
+  pgo::PhaseTimer phase("append_structure");
   DevGraph& d = g->d;
-  HostStructure& H = g->hs;
-  const int n_old = d.n, ne_old = d.ne;
+  pgo::GraphStructure& S = g->gs;
   const int n = (int)g->keys.size(), ne = (int)g->ek1.size(), np = (int)g->pk.size();
-  if (!g->dev_complete || !g->hip_ready || np != d.np || n < n_old || ne < ne_old || (n == n_old && ne == ne_old) ||
-      (size_t)n > g->cap_n || (size_t)ne > g->cap_ne || (int)H.eij.size() != ne_old ||
-      (int)H.erow.size() != n_old + 1 || (int)H.s1pos.size() != ne_old || getenv("PGO_NO_APPEND"))
+  if (!g->dev_complete || !g->hip_ready || np != d.np || S.n != d.n || S.ne() != d.ne || ne < d.ne ||
+      (size_t)n > g->cap_n || (size_t)ne > g->cap_ne || getenv("PGO_NO_APPEND"))
     return 1;
   // the first robust factor on an all-Gaussian device graph: the full upload
   // allocates the loss arrays (and the kernels launched change with it)
   if ((g->n_robust > 0) != (d.eloss != nullptr)) return 1;
-  // the new factors, resolved and in device order
-  std::vector<int> nd(ne - ne_old);
-  std::vector<int2> nij(ne - ne_old);
-  for (int e = ne_old; e < ne; e++) {
-    auto a = g->index.find(g->ek1[e]), b = g->index.find(g->ek2[e]);
-    if (a == g->index.end() || b == g->index.end()) return 1;   // the full path reports it
-    nij[e - ne_old] = make_int2(a->second, b->second);
-    nd[e - ne_old] = e;
-  }
-  {
-    std::vector<int> o(nd.size());
-    for (size_t q = 0; q < o.size(); q++) o[q] = (int)q;
-    std::stable_sort(o.begin(), o.end(), [&](int a, int b) {
-      return nij[a].x != nij[b].x ? nij[a].x < nij[b].x : nij[a].y < nij[b].y;
-    });
-    std::vector<int> nd2(nd.size());
-    std::vector<int2> nij2(nij.size());
-    for (size_t q = 0; q < o.size(); q++) {
-      nd2[q] = nd[o[q]];
-      nij2[q] = nij[o[q]];
-    }
-    nd.swap(nd2);
-    nij.swap(nij2);
-  }
-  if (!nij.empty() && ne_old > 0) {
-    const int2 last = H.eij.back(), f = nij.front();
-    if (f.x < last.x || (f.x == last.x && f.y < last.y)) return 1;   // not an append in device order
-  }
-  phase("resolve");
-  // host structure: device order, block-CSR rows (every row sorted by (column,
-  // code) as build_structure sorts them, codes in their pre-plan form)
-  H.eij.insert(H.eij.end(), nij.begin(), nij.end());
-  H.dorder.insert(H.dorder.end(), nd.begin(), nd.end());
-  std::vector<int> add(n, 0);
-  for (const int2& ij : nij) {
-    add[ij.x]++;
-    add[ij.y]++;
-  }
-  const int ns = 2 * ne;
-  // (into the previous append's arrays: their pages are mapped already;
-  // every element is written below)
-  std::vector<int>& rp = H.spare_rp;
-  std::vector<int>& sc = H.spare_sc;
-  std::vector<int>& se = H.spare_se;
-  rp.resize(n + 1);
-  sc.resize(ns);
-  se.resize(ns);
-  rp[0] = 0;
-  for (int i = 0; i < n; i++) rp[i + 1] = rp[i] + (i < n_old ? H.row_ptr[i + 1] - H.row_ptr[i] : 0) + add[i];
-  // the new slots (row, column, code), by row then (column, code): merged
-  // into the old rows (sorted by (column, code), as build_structure sorts them)
-  std::vector<int3> extra;
-  extra.reserve(2 * nij.size());
-  for (size_t q = 0; q < nij.size(); q++) {
-    const int de = ne_old + (int)q;
-    extra.push_back(make_int3(nij[q].x, nij[q].y, (de << 2) | 2));
-    extra.push_back(make_int3(nij[q].y, nij[q].x, (de << 2) | 1));
-  }
-  std::sort(extra.begin(), extra.end(), [](const int3& a, const int3& b) {
-    return a.x != b.x ? a.x < b.x : a.y != b.y ? a.y < b.y : a.z < b.z;
-  });
-  int prev = 0;   // rows [prev, r) copied whole (H.slot_edge holds pre-plan codes)
-  auto copy_rows = [&](int r) {
-    if (prev >= n_old) return;
-    const int b = H.row_ptr[prev], e0 = H.row_ptr[std::min(r, n_old)];
-    if (e0 > b) {
-      std::copy(H.slot_col.begin() + b, H.slot_col.begin() + e0, sc.begin() + rp[prev]);
-      std::copy(H.slot_edge.begin() + b, H.slot_edge.begin() + e0, se.begin() + rp[prev]);
-    }
-  };
-  for (size_t q = 0; q < extra.size();) {
-    const int i = extra[q].x;
-    size_t q1 = q;
-    while (q1 < extra.size() && extra[q1].x == i) q1++;
-    copy_rows(i);
-    const int b = i < n_old ? H.row_ptr[i] : 0, e0 = i < n_old ? H.row_ptr[i + 1] : 0;
-    int o = rp[i], k = b;
-    for (size_t t = q; t < q1; t++) {   // merge: old slots before an equal (column, code) stay first
-      while (k < e0 && (H.slot_col[k] < extra[t].y || (H.slot_col[k] == extra[t].y && H.slot_edge[k] <= extra[t].z))) {
-        sc[o] = H.slot_col[k];
-        se[o++] = H.slot_edge[k++];
-      }
-      sc[o] = extra[t].y;
-      se[o++] = extra[t].z;
-    }
-    for (; k < e0; k++) {
-      sc[o] = H.slot_col[k];
-      se[o++] = H.slot_edge[k];
-    }
-    prev = i + 1;
-    q = q1;
-  }
-  copy_rows(n);
-  H.row_ptr.swap(rp);
-  H.slot_col.swap(sc);
-  H.slot_edge.swap(se);
-  // gauge: the new factors join components; anchored roots from the priors
-  H.uf.resize(n);
-  for (int i = n_old; i < n; i++) H.uf[i] = i;
-  auto find = [&](int x) {
-    while (H.uf[x] != x) x = H.uf[x] = H.uf[H.uf[x]];
-    return x;
-  };
-  for (const int2& ij : nij) {
-    const int a = find(ij.x), b = find(ij.y);
-    if (a != b) H.uf[a] = b;
-  }
-  {
-    std::vector<char> anchored(n, 0);
-    for (int q = 0; q < np; q++) anchored[find(H.pv[q])] = 1;
-    g->gauge_free = false;
-    for (int i = 0; i < n; i++)
-      if (!anchored[find(i)]) g->gauge_free = true;
-    H.gauge_free = g->gauge_free;
-  }
-  H.prior_ptr.resize(n + 1, H.prior_ptr.empty() ? 0 : H.prior_ptr.back());
-  phase("rows");
-  // rows before r0 (the first with a new slot) and their slots are unchanged:
-  // the host mirrors, the factor -> side-0 slot map and the sweep structure
-  // are updated from there on (h_slot_edge keeps the plan's bits before r0,
-  // as the device copy does)
-  const int r0 = extra.empty() ? n_old : std::min(extra.front().x, n_old);
-  const int k0 = H.row_ptr[r0];
-  g->h_row_ptr.resize(n + 1);
-  std::copy(H.row_ptr.begin() + r0, H.row_ptr.end(), g->h_row_ptr.begin() + r0);
-  g->h_slot_col.resize(ns);
-  std::copy(H.slot_col.begin() + k0, H.slot_col.end(), g->h_slot_col.begin() + k0);
-  if (!g->new_slots.empty()) g->mirror_bound = false;   // (an earlier append not bound yet: its list is stale now)
-  if (g->mirror_bound && (int)g->h_slot_edge.size() >= k0) {
-    // the old slots keep their bound codes (the merge keeps their order), the
-    // new ones get pre-plan codes and are listed for bind_plan
-    std::vector<int> tail_old(g->h_slot_edge.begin() + k0, g->h_slot_edge.end());
-    g->h_slot_edge.resize(ns);
-    size_t kk = 0;
-    for (int o = k0; o < ns; o++) {
-      const int code = H.slot_edge[o];
-      if ((code >> 2) >= ne_old) {
-        g->h_slot_edge[o] = code;
-        g->new_slots.push_back(o);
-      } else {
-        g->h_slot_edge[o] = kk < tail_old.size() ? tail_old[kk] : code;
-        kk++;
-      }
-    }
-    if (kk != tail_old.size()) {   // (cannot happen: the merge keeps every old slot, in order)
-      std::copy(H.slot_edge.begin() + k0, H.slot_edge.end(), g->h_slot_edge.begin() + k0);
-      g->mirror_bound = false;
-      g->new_slots.clear();
-    }
-  } else {
-    g->h_slot_edge.resize(ns);
-    std::copy(H.slot_edge.begin() + k0, H.slot_edge.end(), g->h_slot_edge.begin() + k0);
-    g->mirror_bound = false;
-    g->new_slots.clear();
-  }
-  g->edge_slot0.resize(ne, -1);
-  for (int k = k0; k < ns; k++)
-    if ((H.slot_edge[k] & 1) == 0) g->edge_slot0[H.dorder[H.slot_edge[k] >> 2]] = k;
-  // Cholesky-mode sweep structure (see upload_structure): the new factors come
-  // last in device order, so an old factor keeps its rank among its row's
-  // side-1 factors and moves by its row's shift of s1_ptr
-  int x0 = n_old, y0 = n_old;   // first rows of erow / s1_ptr that change (the new rows always)
-  for (const int2& ij : nij) {
-    x0 = std::min(x0, ij.x);
-    y0 = std::min(y0, ij.y);
-  }
-  std::vector<int>& erow = H.erow;
-  std::vector<int>& s1_ptr = H.s1_ptr;
-  std::vector<int>& s1pos = H.s1pos;
-  {
-    std::vector<int> ecnt(n, 0), scnt(n, 0);   // new factors per row, by side
-    for (const int2& ij : nij) {
-      ecnt[ij.x]++;
-      scnt[ij.y]++;
-    }
-    erow.resize(n + 1, erow.back());
-    s1_ptr.resize(n + 1, s1_ptr.back());
-    for (int i = x0, c = 0; i < n; i++) erow[i + 1] += (c += ecnt[i]);
-    std::vector<int> dy(n + 1, 0);   // new side-1 factors in rows < j
-    for (int j = y0, c = 0; j < n; j++) {
-      dy[j] = c;
-      s1_ptr[j + 1] += (c += scnt[j]);
-    }
-    for (int e = 0; e < ne_old; e++) {
-      const int y = H.eij[e].y;
-      if (y > y0) s1pos[e] += dy[y];
-    }
-    s1pos.resize(ne);
-    std::vector<int> f(n, 0);   // the new factors after the old ones of their row
-    for (size_t q = 0; q < nij.size(); q++) {
-      const int y = nij[q].y;
-      s1pos[ne_old + q] = s1_ptr[y + 1] - scnt[y] + f[y]++;
-    }
-  }
-  g->h_Dc.resize(6 * (size_t)n, 0.0);
-  for (size_t q = 0; q < nij.size(); q++) {   // new side-1 terms, in device order after the old ones
-    const double* o = &g->eom[6 * (size_t)nd[q]];
-    for (int c = 0; c < 6; c++) g->h_Dc[6 * (size_t)nij[q].y + c] += o[c];
-  }
-  std::vector<int> brow(1, 0);
-  for (int r = 0; r < n;) {
-    int r1 = r + 1;
-    while (r1 < n && r1 - r < pgo::kThreads && erow[r1 + 1] - erow[r] <= pgo::kThreads) r1++;
-    brow.push_back(r1);
-    r = r1;
-  }
+  std::vector<int2> new_ij;
+  if (resolve_edges(g, d.ne, new_ij) != PGO_OK) return 1;   // the full path reports it
+  pgo::StructureDelta dl;
+  if (!S.append(n, new_ij, g->eom.data(), d.eloss != nullptr, &dl, &phase)) return 1;
   phase("per-row");
+  const int n_old = dl.n_old, ne_old = dl.ne_old, ns = 2 * ne;
+  const int* nd = S.dorder.data() + ne_old;   // the new factors, device order -> user index
+  const size_t nn = (size_t)(ne - ne_old);
   // the device: new factors, per-row arrays, slots
   HIP_TRY(g, hipStreamSynchronize(d.stream));
   phase("sync");
@@ -1007,73 +588,45 @@ int append_structure(pgo_graph* g) {
   g->saved_valid = false;   // (the snapshot holds the old structure's values; its buffer, sized
                             // for the capacity, is kept: a hipFree would wait for the device)
   phase("free");
-  std::vector<double4> hz(nij.size());
-  std::vector<double2> hom(3 * nij.size());
-  for (size_t q = 0; q < nij.size(); q++) {
-    const int e = nd[q];
-    const double th = g->ez[3 * e + 2];
-    hz[q] = make_double4(g->ez[3 * e], g->ez[3 * e + 1], std::cos(th), std::sin(th));
-    const double* o = &g->eom[6 * (size_t)e];
-    hom[3 * q] = make_double2(o[0], o[1]);
-    hom[3 * q + 1] = make_double2(o[2], o[3]);
-    hom[3 * q + 2] = make_double2(o[4], o[5]);
-  }
+  std::vector<double4> hz(nn);
+  std::vector<double2> hom(3 * nn);
+  pgo::pack_measurements(g->ez.data(), g->eom.data(), nd, nn, hz.data(), hom.data());
   // only what changed: the new factors; the row / slot arrays from the first
   // row with a new slot (earlier rows and their slots are unchanged); the
   // side-1 sums of the rows that gained side-1 terms; whole for the rest
   Staging& sg = g->stage;   // (allocated by upload_structure; staged_h2d falls back to pageable copies)
   RC_TRY(stage_begin(g, sg));
-  RC_TRY(staged_h2d(g, sg, d.eij + ne_old, nij.data(), nij.size()));
+  RC_TRY(staged_h2d(g, sg, d.eij + ne_old, S.eij.data() + ne_old, nn));
   RC_TRY(staged_h2d(g, sg, d.ez + ne_old, hz.data(), hz.size()));
   RC_TRY(staged_h2d(g, sg, d.eom + 3 * (size_t)ne_old, hom.data(), hom.size()));
-  RC_TRY(staged_h2d(g, sg, d.prior_ptr + n_old + 1, H.prior_ptr.data() + n_old + 1, n - n_old));
-  RC_TRY(staged_h2d(g, sg, d.row_ptr + r0 + 1, H.row_ptr.data() + r0 + 1, n - r0));
-  RC_TRY(staged_h2d(g, sg, d.slot_edge + H.row_ptr[r0], g->h_slot_edge.data() + H.row_ptr[r0], ns - H.row_ptr[r0]));
-  RC_TRY(staged_h2d(g, sg, d.slot_col + H.row_ptr[r0], H.slot_col.data() + H.row_ptr[r0], ns - H.row_ptr[r0]));
-  RC_TRY(staged_h2d(g, sg, d.erow + x0 + 1, erow.data() + x0 + 1, n - x0));
-  RC_TRY(staged_h2d(g, sg, d.s1_ptr + y0 + 1, s1_ptr.data() + y0 + 1, n - y0));
-  RC_TRY(staged_h2d(g, sg, d.s1pos, s1pos.data(), ne));
+  RC_TRY(staged_h2d(g, sg, d.prior_ptr + n_old + 1, S.prior_ptr.data() + n_old + 1, n - n_old));
+  RC_TRY(staged_h2d(g, sg, d.row_ptr + dl.r0 + 1, S.row_ptr.data() + dl.r0 + 1, n - dl.r0));
+  RC_TRY(staged_h2d(g, sg, d.slot_edge + dl.k0, S.codes().data() + dl.k0, ns - dl.k0));
+  RC_TRY(staged_h2d(g, sg, d.slot_col + dl.k0, S.slot_col.data() + dl.k0, ns - dl.k0));
+  RC_TRY(staged_h2d(g, sg, d.erow + dl.x0 + 1, S.erow.data() + dl.x0 + 1, n - dl.x0));
+  RC_TRY(staged_h2d(g, sg, d.s1_ptr + dl.y0 + 1, S.s1_ptr.data() + dl.y0 + 1, n - dl.y0));
+  RC_TRY(staged_h2d(g, sg, d.s1pos, S.s1pos.data(), ne));
   std::vector<unsigned char> hl;   // (alive until the stream has drained below: a full staging
   std::vector<double> hk;          // buffer falls back to copies from these)
-  std::vector<int> s1fac;
   if (d.eloss) {
-    hl.resize(nij.size());
-    hk.resize(nij.size());
-    for (size_t q = 0; q < nij.size(); q++) {
-      hl[q] = g->eloss[nd[q]];
-      hk[q] = g->ek[nd[q]];
-    }
-    s1fac.resize(ne);
-    for (int e = 0; e < ne; e++) s1fac[s1pos[e]] = e;
+    gather_losses(g, nd, nn, hl, hk);
     RC_TRY(staged_h2d(g, sg, d.eloss + ne_old, hl.data(), hl.size()));
     RC_TRY(staged_h2d(g, sg, d.ek + ne_old, hk.data(), hk.size()));
-    RC_TRY(staged_h2d(g, sg, d.s1fac, s1fac.data(), s1fac.size()));
+    RC_TRY(staged_h2d(g, sg, d.s1fac, S.s1fac.data(), S.s1fac.size()));
   }
-  {
-    std::vector<int> ys;
-    for (const int2& ij : nij)
-      if (ij.y < n_old) ys.push_back(ij.y);
-    std::sort(ys.begin(), ys.end());
-    ys.erase(std::unique(ys.begin(), ys.end()), ys.end());
-    for (int y : ys) RC_TRY(staged_h2d(g, sg, d.Dc + 6 * (size_t)y, g->h_Dc.data() + 6 * (size_t)y, 6));
-    RC_TRY(staged_h2d(g, sg, d.Dc + 6 * (size_t)n_old, g->h_Dc.data() + 6 * (size_t)n_old, 6 * (size_t)(n - n_old)));
-  }
-  RC_TRY(staged_h2d(g, sg, d.brow, brow.data(), brow.size()));
+  for (int y : dl.dc_rows) RC_TRY(staged_h2d(g, sg, d.Dc + 6 * (size_t)y, S.Dc.data() + 6 * (size_t)y, 6));
+  RC_TRY(staged_h2d(g, sg, d.Dc + 6 * (size_t)n_old, S.Dc.data() + 6 * (size_t)n_old, 6 * (size_t)(n - n_old)));
+  RC_TRY(staged_h2d(g, sg, d.brow, S.brow.data(), S.brow.size()));
   RC_TRY(stage_end(g, sg));
   d.n = n;
   d.ne = ne;
   d.nslots = ns;
-  d.nlb = (int)brow.size() - 1;
-  const double mean_deg = n ? (double)ns / n : 0.0;
-  d.G = 4;
-  while (d.G < 32 && d.G < mean_deg) d.G *= 2;
-  d.G1 = 4;
-  while (d.G1 < 32 && d.G1 < (n ? (double)ne / n : 0.0)) d.G1 *= 2;
+  d.nlb = (int)S.brow.size() - 1;
+  d.G = S.G;
+  d.G1 = S.G1;
   HIP_TRY(g, hipStreamSynchronize(d.stream));
   g->dev_structure = true;
   g->last_upload = 2;
-  if (g->slot_codes_plan && H.row_ptr[r0] > 0) g->slot_codes_mixed = true;   // rows < r0 keep the plan's bits
-  g->bind_row0 = std::min(g->bind_row0, r0);
   if (g->chol_ready) g->plan_stale = true;   // ensure_chol decides what to keep
   phase("upload");
   // the new vertices' values (the resident ones stay bit for bit, unless the
@@ -1138,18 +691,13 @@ int exchange_group(void* ctx, int begin) {
 int bind_plan(pgo_graph* g, bool full);
 
 // Before a PCG linearisation: an in-place append after a Cholesky plan left
-// the device owner bits (and the host mirror h_slot_edge) half the plan's, half
-// pre-plan; upload the pre-plan codes whole so every factor has exactly one
-// `se & 2` slot.
+// the device owner bits (and their host mirror, GraphStructure::codes) half the
+// plan's, half pre-plan; upload the pre-plan codes whole so every factor has
+// exactly one `se & 2` slot.
 int unmix_slot_codes(pgo_graph* g) {
-  if (!g->slot_codes_mixed) return PGO_OK;
-  g->h_slot_edge = g->hs.slot_edge;
-  g->mirror_bound = false;
-  g->new_slots.clear();
-  RC_TRY(h2d(g, g->d.slot_edge, g->h_slot_edge.data(), g->h_slot_edge.size()));
+  if (!g->gs.unbind()) return PGO_OK;
+  RC_TRY(h2d(g, g->d.slot_edge, g->gs.codes().data(), g->gs.codes().size()));
   HIP_TRY(g, hipStreamSynchronize(g->d.stream));
-  g->slot_codes_plan = g->slot_codes_mixed = false;
-  g->bind_row0 = 0;
   return PGO_OK;
 }
 
@@ -1185,7 +733,7 @@ int ensure_chol(pgo_graph* g) {
     for (size_t e = g->plan_edges; e < g->ek1.size(); e++)
       pairs.push_back(make_int2(g->index.at(g->ek1[e]), g->index.at(g->ek2[e])));
     if (n == P.n && pgo::chol_covers(P, pairs)) {
-      pgo::chol_assembly(P, g->h_row_ptr, g->h_slot_col);
+      pgo::chol_assembly(P, g->gs.row_ptr, g->gs.slot_col);
       RC_TRY(bind_plan(g, false));
       g->plan_stale = false;
       g->plan_edges = g->ek1.size();
@@ -1196,8 +744,8 @@ int ensure_chol(pgo_graph* g) {
     // appended poses: into the plan incrementally while the tail is short and
     // the factor has not grown much (then a re-plan below)
     constexpr int kMaxTail = 64;
-    PhaseTimer phase("ensure_chol");
-    if (!getenv("PGO_NO_PLAN_APPEND") && pgo::chol_append(P, n, g->h_row_ptr, g->h_slot_col, pairs, kMaxTail, 1.05)) {
+    pgo::PhaseTimer phase("ensure_chol");
+    if (!getenv("PGO_NO_PLAN_APPEND") && pgo::chol_append(P, n, g->gs.row_ptr, g->gs.slot_col, pairs, kMaxTail, 1.05)) {
       phase("chol_append");
       if (P.schedule_error) return fail(g, PGO_E_HIP, "internal: inconsistent panel schedule");
       drop_graphs(g, true);
@@ -1217,8 +765,8 @@ int ensure_chol(pgo_graph* g) {
       for (int k = 0; k < n0; k++) key[k] = (long long)P.iperm[k] << 32;
       for (int v = n0; v < n; v++) {
         long long base = n;
-        for (int q = g->h_row_ptr[v]; q < g->h_row_ptr[v + 1]; q++) {
-          const int u = g->h_slot_col[q];
+        for (int q = g->gs.row_ptr[v]; q < g->gs.row_ptr[v + 1]; q++) {
+          const int u = g->gs.slot_col[q];
           if (u < v) base = std::min(base, key[u] >> 32);
         }
         key[v] = (base << 32) | (0x7fffffffLL - (v - n0 + 1));   // below the old pose's 0x7fffffff
@@ -1245,8 +793,8 @@ int ensure_chol(pgo_graph* g) {
   g->hook.allgather = exchange_allgather;
   g->hook.broadcast = exchange_broadcast;
   g->hook.group = exchange_group;
-  pgo::chol_analyze(g->chol, g->d.n, g->h_row_ptr, g->h_slot_col);
-  g->bind_row0 = 0;   // (a new order: every owner bit)
+  pgo::chol_analyze(g->chol, g->d.n, g->gs.row_ptr, g->gs.slot_col);
+  g->gs.order_changed();   // (a new order: every owner bit)
   if (g->chol.schedule_error) return fail(g, PGO_E_HIP, "internal: inconsistent panel schedule");
   const auto tb = std::chrono::steady_clock::now();
   RC_TRY(bind_plan(g, true));
@@ -1266,64 +814,37 @@ int ensure_chol(pgo_graph* g) {
 // sources remapped slot -> factor, and the plan (full) or its assembly lists
 // uploaded.
 int bind_plan(pgo_graph* g, bool full) {
-  PhaseTimer phase("bind_plan");
-  {
-    const int n = g->d.n, ne = g->d.ne;
-    const int r0 = std::min(std::max(g->bind_row0, 0), n), k0 = g->h_row_ptr[r0];
-    std::vector<int>& slot_edge = g->h_slot_edge;
-    std::vector<unsigned char>& eside = g->h_eside;
-    if (eside.capacity() < (size_t)ne) eside.reserve(std::max<size_t>(g->cap_ne, ne));
-    eside.resize(ne, 0);
-    // Cholesky-mode linearisation writes each factor's owner block at its
-    // device factor index (one 72-byte record per factor), so the assembly reads V[9 e + q]
-    auto own_bit = [&](int r, int k) {
-      const bool own = g->chol.iperm[r] > g->chol.iperm[g->h_slot_col[k]];
-      slot_edge[k] = (slot_edge[k] & ~2) | (own ? 2 : 0);
-      if (own) eside[slot_edge[k] >> 2] = (unsigned char)(slot_edge[k] & 1);   // one owner slot per factor
-    };
-    if (r0 > 0 && g->mirror_bound) {   // the order kept and every other slot bound: the new slots only
-      for (int k : g->new_slots) {
-        const int r = (int)(std::upper_bound(g->h_row_ptr.begin(), g->h_row_ptr.begin() + n + 1, k) - g->h_row_ptr.begin()) - 1;
-        own_bit(r, k);
-      }
-    } else {
-      host_parallel(n - r0, [&](int a, int b) {
-        for (int r = r0 + a; r < r0 + b; r++)
-          for (int k = g->h_row_ptr[r]; k < g->h_row_ptr[r + 1]; k++) own_bit(r, k);
-      });
-    }
-    std::vector<int>& src = g->chol.asm_src;
-    host_parallel((int)src.size(), [&](int q0, int q1) {
-      for (int q = q0; q < q1; q++)   // (~slot: not yet bound; kept ones are factor indices already)
-        if (src[q] < 0) src[q] = slot_edge[~src[q]] >> 2;
-    });
-    g->chol.asm_bound = true;
-    phase("owners");
-    const hipError_t e = full ? pgo::chol_upload(g->chol, g->d.stream) : pgo::chol_upload_assembly(g->chol, g->d.stream);
-    if (e != hipSuccess) {
-      pgo::chol_free(g->chol);
-      return fail(g, e == hipErrorOutOfMemory ? PGO_E_NOMEM : PGO_E_HIP,
-                  std::string("Cholesky plan upload: ") + hipGetErrorString(e));
-    }
-    phase("chol_upload");
-    if (!g->d.eside) RC_TRY(dev_alloc(g, &g->d.eside, std::max<size_t>(g->cap_ne, g->d.ne)));
-    if (g->stage.buf) {   // pinned staging: the copies (and the fronts' zeroing) run on unsynchronised
-      RC_TRY(stage_begin(g, g->stage));
-      RC_TRY(staged_h2d(g, g->stage, g->d.eside, eside.data(), eside.size()));
-      RC_TRY(staged_h2d(g, g->stage, g->d.slot_edge + k0, slot_edge.data() + k0, slot_edge.size() - k0));
-      RC_TRY(stage_end(g, g->stage));
-    } else {
-      RC_TRY(h2d(g, g->d.eside, eside.data(), eside.size()));
-      RC_TRY(h2d(g, g->d.slot_edge + k0, slot_edge.data() + k0, slot_edge.size() - k0));
-      HIP_TRY(g, hipStreamSynchronize(g->d.stream));
-    }
-    g->slot_codes_plan = true;
-    g->slot_codes_mixed = false;
-    g->bind_row0 = n;
-    g->mirror_bound = true;
-    g->new_slots.clear();
-    phase("slots");
+  pgo::PhaseTimer phase("bind_plan");
+  const pgo::SlotRange up = g->gs.bind(g->chol.iperm);
+  const std::vector<int>& slot_edge = g->gs.codes();
+  const std::vector<unsigned char>& eside = g->gs.eside();
+  std::vector<int>& src = g->chol.asm_src;
+  pgo::host_parallel((int)src.size(), [&](int q0, int q1) {
+    for (int q = q0; q < q1; q++)   // (~slot: not yet bound; kept ones are factor indices already)
+      if (src[q] < 0) src[q] = slot_edge[~src[q]] >> 2;
+  });
+  g->chol.asm_bound = true;
+  phase("owners");
+  const hipError_t e = full ? pgo::chol_upload(g->chol, g->d.stream) : pgo::chol_upload_assembly(g->chol, g->d.stream);
+  if (e != hipSuccess) {
+    pgo::chol_free(g->chol);
+    g->gs.order_changed();   // (the device never got these bits: the next bind uploads every slot)
+    return fail(g, e == hipErrorOutOfMemory ? PGO_E_NOMEM : PGO_E_HIP,
+                std::string("Cholesky plan upload: ") + hipGetErrorString(e));
   }
+  phase("chol_upload");
+  if (!g->d.eside) RC_TRY(dev_alloc(g, &g->d.eside, std::max<size_t>(g->cap_ne, g->d.ne)));
+  if (g->stage.buf) {   // pinned staging: the copies (and the fronts' zeroing) run on unsynchronised
+    RC_TRY(stage_begin(g, g->stage));
+    RC_TRY(staged_h2d(g, g->stage, g->d.eside, eside.data(), eside.size()));
+    RC_TRY(staged_h2d(g, g->stage, g->d.slot_edge + up.begin, slot_edge.data() + up.begin, (size_t)(up.end - up.begin)));
+    RC_TRY(stage_end(g, g->stage));
+  } else {
+    RC_TRY(h2d(g, g->d.eside, eside.data(), eside.size()));
+    RC_TRY(h2d(g, g->d.slot_edge + up.begin, slot_edge.data() + up.begin, (size_t)(up.end - up.begin)));
+    HIP_TRY(g, hipStreamSynchronize(g->d.stream));
+  }
+  phase("slots");
   return PGO_OK;
 }
 
@@ -1394,7 +915,7 @@ int graph_factor_solve(pgo_graph* g, int nb, double* x, long long xstride, bool 
   }
   auto capture = [&](hipGraphExec_t* exec, bool factor) -> int {
     if (*exec) return PGO_OK;
-    PhaseTimer phase("graph_capture");
+    pgo::PhaseTimer phase("graph_capture");
     destroy_stale_graphs(g);
     hipGraph_t graph = nullptr;
     HIP_TRY(g, hipStreamBeginCapture(d.stream, hipStreamCaptureModeThreadLocal));
@@ -1900,7 +1421,7 @@ int pgo_get_edge_weights(pgo_graph* g, size_t first, size_t n, double* out) {
   (void)hipFree(dw);
   HIP_TRY(g, e);
   for (size_t de = 0; de < ne; de++) {
-    const size_t u = (size_t)g->hs.dorder[de];
+    const size_t u = (size_t)g->gs.dorder[de];
     if (u >= first && u < first + n) out[u - first] = hw[de];
   }
   return PGO_OK;
@@ -2073,7 +1594,7 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
   double lam = p.lambda_initial, factor = p.lambda_factor;
   int iters = 0, inner = 0;
   int status = PGO_OK;
-  if (p.algorithm == PGO_ALG_GN && g->gauge_free && d.n > 0 && !(err <= p.error_tol)) {
+  if (p.algorithm == PGO_ALG_GN && g->gs.gauge_free && d.n > 0 && !(err <= p.error_tol)) {
     st.status = PGO_E_INDETERMINANT;
     if (stats) *stats = st;
     return fail(g, PGO_E_INDETERMINANT,
@@ -2607,26 +2128,29 @@ int pgo_get_kernel_profile(const pgo_graph* g, double* out, int cap) {
   return pgo::kFamCount;
 }
 
+// diagnostics: a plan of the host graph as it stands (no device state)
+static int analyze_host_graph(pgo_graph* g, pgo::GraphStructure& S, pgo::CholPlan& P) {
+  RC_TRY(download_values(g));
+  RC_TRY(build_structure(g, S));
+  P.ordering = g->ordering;
+  pgo::chol_analyze(P, S.n, S.row_ptr, S.slot_col);
+  return PGO_OK;
+}
+
 int pgo_debug_parents(pgo_graph* g, int* parent, int cap) {
   if (!g || cap < 0 || (cap > 0 && !parent)) return PGO_E_ARG;
-  RC_TRY(download_values(g));
-  HostStructure H;
-  RC_TRY(build_structure(g, H));
+  pgo::GraphStructure H;
   pgo::CholPlan P;
-  P.ordering = g->ordering;
-  pgo::chol_analyze(P, (int)g->keys.size(), H.row_ptr, H.slot_col);
+  RC_TRY(analyze_host_graph(g, H, P));
   for (int s = 0; s < P.ns && s < cap; s++) parent[s] = P.parent[s];
   return P.ns;
 }
 
 int pgo_debug_partition(pgo_graph* g, int size, int* owner, double* out, int cap) {
   if (!g || size < 1 || cap < 0 || (cap > 0 && (!owner || !out))) return PGO_E_ARG;
-  RC_TRY(download_values(g));
-  HostStructure H;
-  RC_TRY(build_structure(g, H));
+  pgo::GraphStructure H;
   pgo::CholPlan P;
-  P.ordering = g->ordering;
-  pgo::chol_analyze(P, (int)g->keys.size(), H.row_ptr, H.slot_col);
+  RC_TRY(analyze_host_graph(g, H, P));
   std::vector<double> rf;
   double top = 0;
   const std::vector<int> own = pgo::partition_subtrees(P, size, &rf, &top);
@@ -2663,23 +2187,18 @@ int pgo_debug_ordering(pgo_graph* g, int32_t* perm, size_t n) {
     if (n) std::memcpy(perm, g->chol.perm.data(), n * sizeof(int32_t));
     return PGO_OK;
   }
-  HostStructure H;
-  RC_TRY(build_structure(g, H));
+  pgo::GraphStructure H;
   pgo::CholPlan P;
-  P.ordering = g->ordering;
-  pgo::chol_analyze(P, (int)n, H.row_ptr, H.slot_col);
+  RC_TRY(analyze_host_graph(g, H, P));
   if (n) std::memcpy(perm, P.perm.data(), n * sizeof(int32_t));
   return PGO_OK;
 }
 
 int pgo_debug_fronts(pgo_graph* g, int* w, int* m, int* level, int cap) {
   if (!g || cap < 0 || (cap > 0 && (!w || !m || !level))) return PGO_E_ARG;
-  RC_TRY(download_values(g));
-  HostStructure H;
-  RC_TRY(build_structure(g, H));
+  pgo::GraphStructure H;
   pgo::CholPlan P;
-  P.ordering = g->ordering;
-  pgo::chol_analyze(P, (int)g->keys.size(), H.row_ptr, H.slot_col);
+  RC_TRY(analyze_host_graph(g, H, P));
   for (int s = 0; s < P.ns && s < cap; s++) {
     w[s] = P.w[s];
     m[s] = P.m[s];
@@ -2690,12 +2209,9 @@ int pgo_debug_fronts(pgo_graph* g, int* w, int* m, int* level, int cap) {
 
 int pgo_debug_plan(pgo_graph* g, double* out, int cap) {
   if (!g || !out || cap < 16) return PGO_E_ARG;
-  RC_TRY(download_values(g));
-  HostStructure H;
-  RC_TRY(build_structure(g, H));
+  pgo::GraphStructure H;
   pgo::CholPlan P;
-  P.ordering = g->ordering;
-  pgo::chol_analyze(P, (int)g->keys.size(), H.row_ptr, H.slot_col);
+  RC_TRY(analyze_host_graph(g, H, P));
   if (P.schedule_error) return fail(g, PGO_E_HIP, "internal: inconsistent panel schedule");
   // launches: factor = memsets, assembly, rhs permutation, per level extend-add
   // ranks + vector assembly + small classes + per panel diag/trsm/Schur (+look-ahead);
@@ -2775,7 +2291,7 @@ int pgo_debug_linearize(pgo_graph* g, double* hdiag, double* hoff, double* grad,
     }
   if (hoff)
     for (int e = 0; e < d.ne; e++)
-      for (int q = 0; q < 9; q++) hoff[9 * (size_t)e + q] = V[q * (size_t)d.nslots + g->edge_slot0[e]];
+      for (int q = 0; q < 9; q++) hoff[9 * (size_t)e + q] = V[q * (size_t)d.nslots + g->gs.edge_slot0[e]];
   if (grad && !G.empty()) std::memcpy(grad, G.data(), G.size() * 8);
   return PGO_OK;
 }
@@ -2808,7 +2324,7 @@ int pgo_debug_linearize_cholesky(pgo_graph* g, double* hdiag, double* hoff, doub
     }
   if (hoff)
     for (int e = 0; e < d.ne; e++) {
-      const int se = g->h_slot_edge[g->edge_slot0[e]];
+      const int se = g->gs.codes()[g->gs.edge_slot0[e]];
       const size_t de = (size_t)(se >> 2);
       const bool side0_owner = (se & 2) != 0;
       for (int r = 0; r < 3; r++)

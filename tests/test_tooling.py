@@ -4,7 +4,16 @@
   Sanitizer and driven through every entry point by oracle/selftest.c.
 * libpgo's host planning code (symbolic analysis, orderings, partition,
   incremental paths) built the same way (hipcc -Xarch_host) and driven by
-  graphslam_amd/csrc/host_selftest.cpp -- host code only, no GPU.
+  graphslam_amd/csrc/host_selftest.cpp -- host code only, no GPU.  The same
+  binary drives the graph structure module (pgo_structure.cpp) itself: the
+  plan's assembly sources bound through its bind; in-place appends (a new pose
+  with a closure to row 0, a closure into a middle row, a parallel duplicate,
+  three poses at once, two components joined; each once and twice in a row)
+  against a rebuild of the grown graph, array for array with Dc bitwise, and
+  the delta's copy ranges replayed on a device copy; refused appends leaving
+  the structure untouched; the owner-bit transitions (bind, append, incremental
+  bind, unbind, changed order) against a full bind of a rebuild; the packing
+  of measurements and information.
 * libpgo.so carries roctx ranges (pgo_optimize > plan / linearisation >
   lambda_round) for rocprofv3 --marker-trace.
 """
