@@ -85,7 +85,11 @@ struct pgo_graph {
   double plan_ms = 0.0;
   pgo::ExchangeHook hook;                   // the partitioned factorisation's all-gathers (comm)
   bool chol_ready = false;
-  bool handoff_timeout = false;             // the last factorisation's in-launch hand-off gave up (retried once)
+  // pgo_marginal_covariances_all: where every between factor's cross block sits
+  // in the fronts, kept while the plan (its SelPlan::serial) and the factors stay
+  std::vector<int4> sel_etab;
+  unsigned sel_etab_serial = 0;
+  bool handoff_timeout = false;            // the last factorisation's in-launch hand-off gave up (retried once)
   // profiled factorisations (pgo_params.profile_every): every launch timed
   std::vector<hipEvent_t> sev;              // event pairs, one per launch
   std::vector<int> sev_fam;
@@ -1546,6 +1550,46 @@ int pgo_marginal_covariances(pgo_graph* g, size_t n, const uint64_t* keys, doubl
   return PGO_OK;
 }
 
+int pgo_marginal_covariances_all(pgo_graph* g, double* cov, double* edge_cross) {
+  if (!g) return PGO_E_ARG;
+  if (g->keys.empty()) return PGO_OK;
+  if (!cov) return PGO_E_ARG;
+  RC_TRY(ensure_device(g));   // (a factor on a key never inserted: PGO_E_NO_KEY)
+  HIP_TRY(g, hipSetDevice(g->device));
+  g->part_size = 1;   // the pass walks every front: a one-rank plan
+  RC_TRY(ensure_chol(g));
+  DevGraph& d = g->d;
+  d.write_all = 0;
+  HIP_TRY(g, pgo::launch_linearize(d));
+  *g->h_lam = 0.0;
+  HIP_TRY(g, hipMemcpyAsync(g->chol.d_lambda, g->h_lam, sizeof(double), hipMemcpyHostToDevice, d.stream));
+  HIP_TRY(g, pgo::chol_factor(g->chol, d.D, d.V, d.g, 0.0, d.stream, nullptr));
+  int flag = 0;
+  HIP_TRY(g, hipMemcpyAsync(&flag, g->chol.d_flag, sizeof(int), hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(g, hipStreamSynchronize(d.stream));
+  if (flag) return fail(g, PGO_E_INDETERMINANT, "marginals: the linearised system is not positive definite");
+  const size_t ne = edge_cross ? g->ek1.size() : 0;
+  bool changed = false;
+  if (ne && (g->sel_etab_serial != g->chol.sel.serial || g->sel_etab.size() != ne)) {
+    std::vector<int2> pairs(ne);
+    for (size_t e = 0; e < ne; e++) pairs[e] = make_int2(g->index.at(g->ek1[e]), g->index.at(g->ek2[e]));
+    g->sel_etab.resize(ne);
+    pgo::selinv_edge_table(g->chol, pairs.data(), (long long)ne, g->sel_etab.data());
+    g->sel_etab_serial = 0;
+    for (const int4& t : g->sel_etab)
+      if (t.x < 0) return fail(g, PGO_E_HIP, "internal: a factor's block is not in the Cholesky plan's fronts");
+    g->sel_etab_serial = g->chol.sel.serial;
+    changed = true;
+  }
+  const hipError_t e = pgo::chol_selinv(g->chol, g->sel_etab.data(), (long long)ne, changed, cov, edge_cross, d.stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(g, e == hipErrorOutOfMemory ? PGO_E_NOMEM : PGO_E_HIP,
+                std::string("selected inversion: ") + hipGetErrorString(e));
+  }
+  return PGO_OK;
+}
+
 int pgo_error(pgo_graph* g, double* err) {
   if (!g || !err) return PGO_E_ARG;
   RC_TRY(ensure_device(g));
@@ -2262,6 +2306,28 @@ int pgo_debug_plan(pgo_graph* g, double* out, int cap) {
     out[o++] = (double)lv.panels.size();
     out[o++] = small;
     out[o++] = (double)tiles;
+  }
+  return PGO_OK;
+}
+
+int pgo_debug_selinv_plan(pgo_graph* g, double* out, int cap) {
+  if (!g || !out || cap < 4) return PGO_E_ARG;
+  pgo::GraphStructure H;
+  pgo::CholPlan P;
+  RC_TRY(analyze_host_graph(g, H, P));
+  if (P.schedule_error) return fail(g, PGO_E_HIP, "internal: inconsistent panel schedule");
+  const pgo::SelPlan& Q = P.sel;
+  for (int i = 0; i < cap; i++) out[i] = 0.0;
+  out[0] = Q.launches;
+  out[1] = pgo::selinv_flops(P);
+  // Z in the fronts' layout, the panel scratch, the partial products, the read-out buffer
+  out[2] = (double)P.ftotal + (double)Q.gmax + 4096.0 * (double)Q.pmax + 9.0 * ((double)P.n + (double)g->ek1.size());
+  out[3] = (double)Q.levels.size();
+  for (size_t L = 0; L < Q.levels.size() && 4 + (int)L < cap; L++) {   // launches per level, leaves first
+    const pgo::SelLevel& sl = Q.levels[L];
+    int n = (sl.small_cnt > 0) + (sl.gat_cnt > 0);
+    for (const pgo::SelStep& st : sl.steps) n += 2 * (st.tile_cnt > 0) + 1;
+    out[4 + L] = n;
   }
   return PGO_OK;
 }

@@ -140,6 +140,46 @@ struct CholLevel {
   std::vector<double> far_piece_flops;
 };
 
+// Selected inversion (chol_selinv): the entries of H^-1 on the pattern of L,
+// top-down over the levels.  Per level: the small fronts in one launch (one
+// workgroup each, k_selinv_small); the blocked fronts' Z_UU gathered from
+// their parents (k_selinv_gather), then per 64-column pivot block b, from the
+// level's maxblk - 1 down to 0, three launches over every front that has a
+// block b: G = L_Rb X_bb (k_selinv_g), the 64-row tiles of Z_Rb = -Z_RR G with
+// their partial products G' Z_Rb (k_selinv_tile), Z_bb = X'X - the partials in
+// task order (k_selinv_diag).
+struct SelStep {
+  int b;
+  int tile_off, tile_cnt;          // sel.tiles (front, r0, c0, partial slot of the step)
+  int diag_off, diag_cnt;          // sel.diag (front, c0, first partial slot, partials)
+};
+struct SelLevel {                  // same index as CholPlan::levels
+  int small_off = 0, small_cnt = 0;   // CholPlan::small_list: the level's size classes, back to back
+  int gat_off = 0, gat_cnt = 0;       // sel.gather (front, column block): Z_UU of the blocked fronts
+  std::vector<SelStep> steps;
+};
+struct SelPlan {
+  std::vector<SelLevel> levels;
+  std::vector<int2> gather;
+  std::vector<int4> tiles, diag;
+  std::vector<long long> goff;     // [ns] a blocked front's panel scratch (fpad(m) x 64 doubles) within its level
+  long long gmax = 0;              // panel scratch of the largest level (doubles)
+  long long pmax = 0;              // most partial slots (64 x 64 doubles each) of a step
+  int launches = 0;                // kernel launches of the pass (read-out included)
+  unsigned serial = 0;             // bumped by every schedule (device lists, edge tables stale)
+  // ---- device (chol_selinv; released by chol_free)
+  void* d_lists = nullptr;
+  size_t lists_cap = 0;
+  unsigned d_serial = 0;
+  int2* d_gather = nullptr;
+  int4 *d_tiles = nullptr, *d_diag = nullptr;
+  long long* d_goff = nullptr;
+  double *Z = nullptr, *G = nullptr, *part = nullptr, *out = nullptr;
+  long long z_cap = 0, g_cap = 0, part_cap = 0, out_cap = 0;
+  int4* d_etab = nullptr;          // per between factor: (front, row, column, transposed) of its cross block
+  long long etab_cap = 0;
+};
+
 enum { kOrderNd = 0, kOrderAmd = 1 };
 
 struct NumericCap {                // element counts of the numeric workspaces (all lanes)
@@ -224,6 +264,7 @@ struct CholPlan {
   std::vector<long long> xp_loff;       // offset of the item in its owner's payload (doubles)
   std::vector<long long> xp_lstride;    // its owner's payload per lane at that exchange (doubles)
   long long xp_rslot = 0;               // largest payload per rank and lane
+  SelPlan sel;                     // the selected-inversion pass (one-rank plans)
   double flops = 0, nnzl = 0, syrk_flops = 0;
   long long ftotal = 0, ttotal = 0;
   int vtotal = 0;
@@ -397,6 +438,19 @@ hipError_t chol_step_stamps(unsigned long long* out, int slots);
 // reads it (fronts' lower trapezoids, frontal vectors, diagonal inverses), every lane
 hipError_t chol_debug_poison(const CholPlan& P, hipStream_t s);
 hipError_t chol_marginals(const CholPlan& P, const int* poses, int n, double* out, hipStream_t s);
+// host: where the cross block of H^-1 of each pose pair (old indices) sits in
+// the fronts: (front, scalar row, scalar column, 1 = the stored block has the
+// second pose's rows); a pair of one pose twice reads its diagonal block
+void selinv_edge_table(const CholPlan& P, const int2* pairs, long long ne, int4* out);
+// host: algorithmic flops of the pass (diagnostics)
+double selinv_flops(const CholPlan& P);
+// after chol_factor (one-rank plan, lane 0, pivots checked): every pose's 3x3
+// block of (L L^T)^{-1} (old index, row-major) into host cov, and with cross
+// != nullptr the ne blocks of etab (host; uploaded when etab_changed or first
+// used) into host cross.  The fronts and the diagonal inverses are only read:
+// Z lives in a workspace of its own, with the fronts' layout and offsets.
+hipError_t chol_selinv(CholPlan& P, const int4* etab, long long ne, bool etab_changed, double* cov, double* cross,
+                       hipStream_t s);
 // after chol_factor: x = L^-T y = (L L^T)^{-1} scale_b b, indexed by old pose
 // lane y's solution to x + y * xstride
 hipError_t chol_solve(const CholPlan& P, double* x, hipStream_t s, int nb = 1, long long xstride = 0,

@@ -2657,6 +2657,300 @@ __global__ __launch_bounds__(256) void k_marginals(CholDev c, const int2* __rest
   }
 }
 
+// ------------------------------------------------------------ selected inversion
+// Z = (L L')^-1 on the pattern of L (Takahashi's recurrence), every pose's
+// marginal covariance and every factor's cross-covariance in one top-down
+// pass (pgo_chol.h SelPlan).  Z keeps the fronts' layout in a workspace of its
+// own (Z + foff[s]); F and Tinv are only read.  Front s, pivot block b
+// (columns [c0, c0 + nb)), R = the rows below it, X = the inverted diagonal
+// tile, L_Rb the stored panel:
+//   G = L_Rb X,   Z_Rb = -Z_RR G,   Z_bb = X'X - G' Z_Rb
+// with Z_UU (U = the rows below the pivots) copied out of the parent's Z
+// first.  A packed front holds Z's lower triangle (the mirror read
+// transposed); a small front holds both triangles.  Every sum runs in a fixed
+// order (no atomics): two passes agree bit for bit.
+__device__ __forceinline__ double zsym(const double* Zs, int m, bool pk, int i, int j) {
+  if (pk && i < j) {
+    const int t = i;
+    i = j;
+    j = t;
+  }
+  return Zs[fcol_off(m, pk, j) + i];
+}
+
+// one workgroup per small front (m <= 128, w <= 32: one pivot block)
+__global__ __launch_bounds__(256) void k_selinv_small(CholDev c, double* __restrict__ Z,
+                                                      const int* __restrict__ list) {
+  __shared__ double Gs[(kSmallFront - 3) * (kWaveW + 1)];
+  __shared__ double Xs[kWaveW * (kWaveW + 1)];
+  __shared__ int rel[kSmallFront];
+  constexpr int LD = kWaveW + 1;
+  const int tid = threadIdx.x, s = list[blockIdx.x];
+  const int m = c.m[s], w = c.w[s], nu = m - w;
+  const double* L = c.F + c.foff[s];
+  const double* X = c.Tinv + c.toff[s];   // row-major, ld 64
+  double* Zs = Z + c.foff[s];
+  if (nu > 0) {
+    const int p = c.parent[s], mp = c.m[p];
+    const bool pkp = front_packed(mp, c.w[p]);
+    const double* Zp = Z + c.foff[p];
+    const int* er = c.ea_rel + c.ea_ptr[s];
+    for (int t = tid; t < nu; t += 256) rel[t] = 3 * er[t / 3] + t % 3;
+    __syncthreads();
+    for (int idx = tid; idx < nu * nu; idx += 256) {
+      const int i = idx % nu, j = idx / nu;
+      Zs[(size_t)(w + j) * m + w + i] = zsym(Zp, mp, pkp, rel[i], rel[j]);
+    }
+  }
+  for (int idx = tid; idx < w * w; idx += 256) {
+    const int k = idx / w, j = idx % w;
+    Xs[k * LD + j] = k >= j ? X[k * 64 + j] : 0.0;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < nu * w; idx += 256) {
+    const int r = idx % nu, j = idx / nu;
+    double acc = 0;
+    for (int k = j; k < w; k++) acc = fma(L[w + r + (size_t)k * m], Xs[k * LD + j], acc);
+    Gs[r * LD + j] = acc;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < nu * w; idx += 256) {
+    const int r = idx % nu, j = idx / nu;
+    double acc = 0;
+    for (int k = 0; k < nu; k++) acc = fma(Zs[(size_t)(w + k) * m + w + r], Gs[k * LD + j], acc);
+    Zs[(size_t)j * m + w + r] = -acc;
+    Zs[(size_t)(w + r) * m + j] = -acc;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < w * w; idx += 256) {
+    const int i = idx % w, j = idx / w;
+    if (i < j) continue;
+    double acc = 0;
+    for (int k = i; k < w; k++) acc = fma(Xs[k * LD + i], Xs[k * LD + j], acc);
+    for (int r = 0; r < nu; r++) acc = fma(-Gs[r * LD + i], Zs[(size_t)j * m + w + r], acc);
+    Zs[(size_t)j * m + i] = acc;
+    Zs[(size_t)i * m + j] = acc;
+  }
+}
+
+// Z_UU of a blocked front from its parent's Z: task (front, column block), the
+// block's columns at or past w, rows from the diagonal down
+__global__ __launch_bounds__(256) void k_selinv_gather(CholDev c, double* __restrict__ Z,
+                                                       const int2* __restrict__ tasks) {
+  __shared__ int relc[64];
+  const int tid = threadIdx.x;
+  const int2 t = tasks[blockIdx.x];
+  const int s = t.x, m = c.m[s], w = c.w[s];
+  const int j0 = max(64 * t.y, w), j1 = min(64 * t.y + 64, m);
+  const int p = c.parent[s], mp = c.m[p];
+  const bool pkp = front_packed(mp, c.w[p]);
+  const double* Zp = Z + c.foff[p];
+  const int* er = c.ea_rel + c.ea_ptr[s];
+  double* Zs = Z + c.foff[s];
+  if (tid < j1 - j0) relc[tid] = 3 * er[(j0 + tid - w) / 3] + (j0 + tid - w) % 3;
+  __syncthreads();
+  for (int i = j0 + tid; i < m; i += 256) {
+    const int pi = 3 * er[(i - w) / 3] + (i - w) % 3;
+    const int je = min(i + 1, j1);
+    for (int j = j0; j < je; j++) Zs[fcol_off(m, true, j) + i] = zsym(Zp, mp, pkp, pi, relc[j - j0]);
+  }
+}
+
+// G = L_Rb X_bb into the front's panel scratch (ld fpad(m), indexed by the
+// front's row; columns past nb zero): task (front, r0, c0, -), 64 rows
+__global__ __launch_bounds__(256) void k_selinv_g(CholDev c, const int4* __restrict__ tasks,
+                                                  const long long* __restrict__ goff, double* __restrict__ G) {
+  __shared__ double Xs[64 * 65], Ls[64 * 65];
+  const int tid = threadIdx.x;
+  const int4 t = tasks[blockIdx.x];
+  const int s = t.x, r0 = t.y, c0 = t.z, m = c.m[s], w = c.w[s], nb = min(64, w - c0);
+  const double* X = c.Tinv + c.toff[s] + (size_t)(c0 >> 6) * 4096;   // row-major
+  const double* Lb = fcol(c.F + c.foff[s], m, true, c0);
+  const int ld = fld(m, true, c0), mp = fpad(m);
+  for (int idx = tid; idx < 4096; idx += 256) {
+    const int k = idx >> 6, j = idx & 63;
+    Xs[k * 65 + j] = (k < nb && j <= k) ? X[idx] : 0.0;
+    const int r = idx & 63, kk = idx >> 6;   // L(r0 + r, c0 + kk), consecutive rows
+    Ls[kk * 65 + r] = (r0 + r < m && kk < nb) ? Lb[(r0 + r) + (size_t)kk * ld] : 0.0;
+  }
+  __syncthreads();
+  double* Gs = G + goff[s];
+  const int r = tid & 63;
+  for (int u = 0; u < 16; u++) {
+    const int j = (tid >> 6) + 4 * u;
+    double acc = 0;
+    for (int k = j; k < nb; k++) acc = fma(Ls[k * 65 + r], Xs[k * 65 + j], acc);
+    if (r0 + r < m) Gs[r0 + r + (size_t)j * mp] = acc;
+  }
+}
+
+// a 64-row tile of Z_Rb = -Z_RR G (v_mfma_f64_16x16x4_f64: wave v the tile's
+// rows [16 v, 16 v + 16), K over R in chunks of 32 staged in LDS -- the next
+// chunk's loads in flight in registers while this one multiplies --, the part
+// of Z_RR above the diagonal read as the transpose of its mirror), then the
+// tile's share of G' Z_Rb to its partial slot: task (front, r0, c0, slot)
+__global__ __launch_bounds__(256) void k_selinv_tile(CholDev c, double* __restrict__ Z,
+                                                     const int4* __restrict__ tasks,
+                                                     const long long* __restrict__ goff,
+                                                     const double* __restrict__ G, double* __restrict__ part) {
+  constexpr int LD = 68, KC = 32;
+  __shared__ double smem[2 * KC * LD];
+  double* As = smem;             // [KC][LD]: Z_RR(r0 + r, k0 + kk) at kk * LD + r
+  double* Bs = smem + KC * LD;   // [KC][LD]: G(k0 + kk, j) at kk * LD + j
+  double* Zt = smem;             // after the K loop: the tile, ld 65
+  static_assert(64 * 65 <= 2 * KC * LD, "the tile fits the staging buffers");
+  const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, li = l & 15, kq = l >> 4;
+  const int4 t = tasks[blockIdx.x];
+  const int s = t.x, r0 = t.y, c0 = t.z, m = c.m[s], w = c.w[s], nb = min(64, w - c0), rs = c0 + nb;
+  const int mp = fpad(m);
+  double* Zs = Z + c.foff[s];
+  const double* Gs = G + goff[s];
+  d4 acc[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ct++) acc[ct] = d4{0, 0, 0, 0};
+  double ra[8], rb[8];
+  // chunk k0 into registers.  At or above the diagonal (k0 >= r0 + 63) thread
+  // (kk = tid & 31, r = tid / 32 + 8 u) reads Z(k, r), consecutive k; else
+  // (r = tid & 63, kk = tid / 64 + 4 u) reads Z(r, k) or its mirror
+  auto fetch = [&](int k0) {
+    if (k0 >= r0 + 63) {
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        const int gi = k0 + (tid & 31), gj = r0 + (tid >> 5) + 8 * u;
+        ra[u] = (gi < m && gj < m) ? Zs[fcol_off(m, true, gj) + gi] : 0.0;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; u++) {
+        const int gi = r0 + (tid & 63), gj = k0 + (tid >> 6) + 4 * u;
+        ra[u] = (gi < m && gj < m) ? zsym(Zs, m, true, gi, gj) : 0.0;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; u++) {
+      const int gk = k0 + (tid & 31), j = (tid >> 5) + 8 * u;
+      rb[u] = gk < m ? Gs[gk + (size_t)j * mp] : 0.0;
+    }
+  };
+  if (rs < m) fetch(rs);
+  for (int k0 = rs; k0 < m; k0 += KC) {
+    if (k0 >= r0 + 63) {
+#pragma unroll
+      for (int u = 0; u < 8; u++) As[(tid & 31) * LD + (tid >> 5) + 8 * u] = ra[u];
+    } else {
+#pragma unroll
+      for (int u = 0; u < 8; u++) As[((tid >> 6) + 4 * u) * LD + (tid & 63)] = ra[u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; u++) Bs[(tid & 31) * LD + (tid >> 5) + 8 * u] = rb[u];
+    __syncthreads();
+    if (k0 + KC < m) fetch(k0 + KC);
+#pragma unroll
+    for (int ks = 0; ks < KC / 4; ks++) {
+      const double a = As[(4 * ks + kq) * LD + 16 * wv + li];
+#pragma unroll
+      for (int ct = 0; ct < 4; ct++)
+        acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[(4 * ks + kq) * LD + 16 * ct + li], acc[ct], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  // Z_Rb tile out (rows < m, columns < nb) and into LDS for the partial
+#pragma unroll
+  for (int ct = 0; ct < 4; ct++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int i = 16 * wv + kq + 4 * r, j = 16 * ct + li;
+      const double v = -acc[ct][r];
+      Zt[i * 65 + j] = v;   // (rows past m: zero, their A rows were)
+      if (r0 + i < m && j < nb) Zs[fcol_off(m, true, c0 + j) + r0 + i] = v;
+    }
+  __syncthreads();
+  // partial(i, j) = sum_r G(r0 + r, i) Zt(r, j): wave v the rows [16 v, 16 v + 16)
+#pragma unroll
+  for (int ct = 0; ct < 4; ct++) acc[ct] = d4{0, 0, 0, 0};
+  for (int ks = 0; ks < 16; ks++) {
+    const int r = 4 * ks + kq;
+    const double a = (r0 + r < m) ? Gs[r0 + r + (size_t)(16 * wv + li) * mp] : 0.0;
+#pragma unroll
+    for (int ct = 0; ct < 4; ct++)
+      acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Zt[r * 65 + 16 * ct + li], acc[ct], 0, 0, 0);
+  }
+  double* Pp = part + (size_t)t.w * 4096;
+#pragma unroll
+  for (int ct = 0; ct < 4; ct++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) Pp[(16 * wv + kq + 4 * r) + (16 * ct + li) * 64] = acc[ct][r];
+}
+
+// Z_bb = X'X - the step's partials in task order: task (front, c0, first
+// partial, partials); the lower triangle (a packed front's storage)
+__global__ __launch_bounds__(256) void k_selinv_diag(CholDev c, double* __restrict__ Z,
+                                                     const int4* __restrict__ tasks,
+                                                     const double* __restrict__ part) {
+  __shared__ double Xs[64 * 65];
+  const int tid = threadIdx.x;
+  const int4 t = tasks[blockIdx.x];
+  const int s = t.x, c0 = t.y, m = c.m[s], w = c.w[s], nb = min(64, w - c0);
+  const double* X = c.Tinv + c.toff[s] + (size_t)(c0 >> 6) * 4096;
+  for (int idx = tid; idx < 4096; idx += 256) {
+    const int k = idx >> 6, j = idx & 63;
+    Xs[k * 65 + j] = (k < nb && j <= k) ? X[idx] : 0.0;
+  }
+  __syncthreads();
+  double* Zs = Z + c.foff[s];
+  const int i = tid & 63, jb = tid >> 6;   // the thread's elements: (i, jb + 4 u)
+  double acc[16];
+#pragma unroll
+  for (int u = 0; u < 16; u++) {
+    const int j = jb + 4 * u;
+    double a = 0;
+    if (i >= j && i < nb)
+      for (int k = i; k < nb; k++) a = fma(Xs[k * 65 + i], Xs[k * 65 + j], a);
+    acc[u] = a;
+  }
+  for (int q = 0; q < t.w; q++) {   // (a partial's 16 loads in flight at once, subtracted in task order)
+    const double* Pp = part + (size_t)(t.z + q) * 4096 + i + jb * 64;
+    double v[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) v[u] = Pp[u * 256];
+#pragma unroll
+    for (int u = 0; u < 16; u++) acc[u] -= v[u];
+  }
+#pragma unroll
+  for (int u = 0; u < 16; u++) {
+    const int j = jb + 4 * u;
+    if (i >= j && i < nb) Zs[fcol_off(m, true, c0 + j) + c0 + i] = acc[u];
+  }
+}
+
+// read-out: thread q < n the diagonal block of new pose q to its old index,
+// thread n + e the cross block of table entry e
+__global__ __launch_bounds__(256) void k_selinv_out(CholDev c, const double* __restrict__ Z, int n,
+                                                    const int4* __restrict__ etab, long long ne,
+                                                    double* __restrict__ out) {
+  const long long q = blockIdx.x * 256LL + threadIdx.x;
+  if (q >= n + ne) return;
+  int s, li, lj, tr = 0;
+  long long o;
+  if (q < n) {
+    s = c.dg_front[q];
+    li = lj = 3 * c.dg_loc[q];
+    o = 9LL * c.perm[q];
+  } else {
+    const int4 e = etab[q - n];
+    s = e.x;
+    li = e.y;
+    lj = e.z;
+    tr = e.w;
+    o = 9LL * q;
+  }
+  const int m = c.m[s];
+  const bool pk = front_packed(m, c.w[s]);
+  const double* Zs = Z + c.foff[s];
+  for (int a = 0; a < 3; a++)
+    for (int b = 0; b < 3; b++) out[o + (tr ? 3 * b + a : 3 * a + b)] = zsym(Zs, m, pk, li + a, lj + b);
+}
+
 // ------------------------------------------------------------ host drivers
 #define CH_TRY(x)                       \
   do {                                  \
@@ -2924,8 +3218,11 @@ hipError_t chol_upload(CholPlan& P, hipStream_t s) {
   return hipSuccess;   // (the fronts' zeroing runs on, stream-ordered before any use)
 }
 
+static void free_selinv(SelPlan& Q);
+
 void chol_free(CholPlan& P) {
   free_numeric(P);
+  free_selinv(P.sel);
   if (P.d_blob) (void)hipFree(P.d_blob);
   if (P.h_blob) (void)hipHostFree(P.h_blob);
   for (hipEvent_t e : P.evs)
@@ -3381,6 +3678,94 @@ hipError_t chol_marginals(const CholPlan& P, const int* poses, int n, double* ou
   if (d_scr) (void)hipFree(d_scr);
   if (d_out) (void)hipFree(d_out);
   return e;
+}
+
+static void free_selinv(SelPlan& Q) {
+  void* ptrs[] = {Q.d_lists, Q.Z, Q.G, Q.part, Q.out, Q.d_etab};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  Q.d_lists = nullptr;
+  Q.Z = Q.G = Q.part = Q.out = nullptr;
+  Q.d_etab = nullptr;
+  Q.lists_cap = 0;
+  Q.z_cap = Q.g_cap = Q.part_cap = Q.out_cap = Q.etab_cap = 0;
+  Q.d_gather = nullptr;
+  Q.d_tiles = Q.d_diag = nullptr;
+  Q.d_goff = nullptr;
+}
+
+template <class T>
+static hipError_t grow(T** p, long long* cap, long long need) {
+  if (*p && *cap >= need) return hipSuccess;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  need += need / 32 + 64;
+  CH_TRY(hipMalloc((void**)p, need * sizeof(T)));
+  *cap = need;
+  return hipSuccess;
+}
+
+hipError_t chol_selinv(CholPlan& P, const int4* etab, long long ne, bool etab_changed, double* cov, double* cross,
+                       hipStream_t s) {
+  if (P.n == 0) return hipSuccess;
+  if (P.part_size > 1 || P.sel.levels.size() != P.levels.size()) return hipErrorInvalidValue;
+  SelPlan& Q = P.sel;
+  if (!cross) ne = 0;
+  CH_TRY(hipStreamSynchronize(s));   // (buffers below may be replaced)
+  if (!Q.d_lists || Q.d_serial != Q.serial) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b0 = 0, b1 = al(Q.gather.size() * sizeof(int2)),
+                 b2 = al(Q.tiles.size() * sizeof(int4)), b3 = al(Q.diag.size() * sizeof(int4)),
+                 b4 = al(Q.goff.size() * sizeof(long long)), tot = b0 + b1 + b2 + b3 + b4 + 256;
+    if (tot > Q.lists_cap) {
+      if (Q.d_lists) (void)hipFree(Q.d_lists);
+      Q.d_lists = nullptr;
+      Q.lists_cap = 0;
+      CH_TRY(hipMalloc(&Q.d_lists, tot + tot / 16));
+      Q.lists_cap = tot + tot / 16;
+    }
+    char* d = (char*)Q.d_lists;
+    Q.d_gather = (int2*)(d + b0);
+    Q.d_tiles = (int4*)(d + b0 + b1);
+    Q.d_diag = (int4*)(d + b0 + b1 + b2);
+    Q.d_goff = (long long*)(d + b0 + b1 + b2 + b3);
+    CH_TRY(hipMemcpyAsync(Q.d_gather, Q.gather.data(), Q.gather.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    CH_TRY(hipMemcpyAsync(Q.d_tiles, Q.tiles.data(), Q.tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+    CH_TRY(hipMemcpyAsync(Q.d_diag, Q.diag.data(), Q.diag.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+    CH_TRY(hipMemcpyAsync(Q.d_goff, Q.goff.data(), Q.goff.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    CH_TRY(hipStreamSynchronize(s));   // (pageable sources)
+    Q.d_serial = Q.serial;
+  }
+  CH_TRY(grow(&Q.Z, &Q.z_cap, std::max<long long>(P.ftotal, 1)));
+  CH_TRY(grow(&Q.G, &Q.g_cap, std::max<long long>(Q.gmax, 1)));
+  CH_TRY(grow(&Q.part, &Q.part_cap, std::max<long long>(Q.pmax, 1) * 4096));
+  CH_TRY(grow(&Q.out, &Q.out_cap, 9LL * (P.n + ne)));
+  if (ne > 0 && (etab_changed || !Q.d_etab || Q.etab_cap < ne)) {
+    CH_TRY(grow(&Q.d_etab, &Q.etab_cap, ne));
+    CH_TRY(hipMemcpyAsync(Q.d_etab, etab, ne * sizeof(int4), hipMemcpyHostToDevice, s));
+    CH_TRY(hipStreamSynchronize(s));
+  }
+  const CholDev c = dev_view(P);
+  for (int L = (int)Q.levels.size() - 1; L >= 0; L--) {
+    const SelLevel& sl = Q.levels[L];
+    if (sl.small_cnt) k_selinv_small<<<sl.small_cnt, 256, 0, s>>>(c, Q.Z, P.d_small + sl.small_off);
+    if (sl.gat_cnt) k_selinv_gather<<<sl.gat_cnt, 256, 0, s>>>(c, Q.Z, Q.d_gather + sl.gat_off);
+    for (const SelStep& st : sl.steps) {
+      if (st.tile_cnt) {
+        k_selinv_g<<<st.tile_cnt, 256, 0, s>>>(c, Q.d_tiles + st.tile_off, Q.d_goff, Q.G);
+        k_selinv_tile<<<st.tile_cnt, 256, 0, s>>>(c, Q.Z, Q.d_tiles + st.tile_off, Q.d_goff, Q.G, Q.part);
+      }
+      k_selinv_diag<<<st.diag_cnt, 256, 0, s>>>(c, Q.Z, Q.d_diag + st.diag_off, Q.part);
+    }
+    CH_TRY(hipGetLastError());
+  }
+  const long long nt = P.n + ne;
+  k_selinv_out<<<(unsigned)((nt + 255) / 256), 256, 0, s>>>(c, Q.Z, P.n, Q.d_etab, ne, Q.out);
+  CH_TRY(hipGetLastError());
+  CH_TRY(hipMemcpyAsync(cov, Q.out, 9LL * P.n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (ne > 0) CH_TRY(hipMemcpyAsync(cross, Q.out + 9LL * P.n, 9LL * ne * sizeof(double), hipMemcpyDeviceToHost, s));
+  return hipStreamSynchronize(s);
 }
 
 hipError_t chol_solve(const CholPlan& P, double* x, hipStream_t s, int nb, long long xstride, LaunchProfile* prof,

@@ -418,6 +418,96 @@ struct LevelLists {
 // The plan's schedules from its fronts (chol_analyze's second half; the
 // incremental append re-runs it on the updated fronts): the subtree partition,
 // the level schedules and task lists, then the H assembly lists.
+// The selected-inversion pass's launch lists (pgo_chol.h SelPlan) from the
+// level lists: rebuilt with every schedule, so a re-plan and an incremental
+// append carry them too.  A partitioned plan has none (the pass walks every
+// front: pgo_marginal_covariances_all plans for one rank).
+static void selinv_schedule(CholPlan& P) {
+  SelPlan& Q = P.sel;
+  Q.levels.clear();
+  Q.gather.clear();
+  Q.tiles.clear();
+  Q.diag.clear();
+  Q.goff.assign(P.ns, 0);
+  Q.gmax = Q.pmax = 0;
+  Q.launches = 0;
+  static std::atomic<unsigned> serial{0};   // (unique over plans: a handle's edge table is keyed by it)
+  Q.serial = ++serial;
+  if (P.part_size > 1) return;
+  Q.levels.resize(P.levels.size());
+  Q.launches = 1;   // the read-out
+  std::vector<int> big;   // the level's blocked fronts, in level order
+  for (size_t L = 0; L < P.levels.size(); L++) {
+    const CholLevel& lv = P.levels[L];
+    SelLevel& sl = Q.levels[L];
+    const int* fr = P.level_fronts.data() + lv.front_off;
+    // (every front that is not packed is in one of the level's wavefront
+    // classes, and those sit back to back in small_list)
+    sl.small_off = lv.small.empty() ? 0 : lv.small.front().off;
+    for (const SmallClass& sc : lv.small) sl.small_cnt += sc.cnt;
+    sl.gat_off = (int)Q.gather.size();
+    long long g = 0;
+    int maxblk = 0;
+    big.clear();
+    for (int q = 0; q < lv.front_cnt; q++) {
+      const int s = fr[q], m = P.m[s], w = P.w[s];
+      if (!front_packed(m, w)) continue;
+      big.push_back(s);
+      Q.goff[s] = g;
+      g += 64LL * fpad(m);
+      maxblk = std::max(maxblk, (w + 63) / 64);
+      if (m > w)
+        for (int cb = w / 64; 64 * cb < m; cb++) Q.gather.push_back(make_int2(s, cb));
+    }
+    Q.gmax = std::max(Q.gmax, g);
+    sl.gat_cnt = (int)Q.gather.size() - sl.gat_off;
+    Q.launches += (sl.small_cnt > 0) + (sl.gat_cnt > 0);
+    for (int b = maxblk - 1; b >= 0; b--) {
+      SelStep st{b, (int)Q.tiles.size(), 0, (int)Q.diag.size(), 0};
+      int slot = 0;
+      for (int s : big) {
+        const int m = P.m[s], w = P.w[s], c0 = 64 * b;
+        if (c0 >= w) continue;
+        const int rs = c0 + std::min(64, w - c0), p0 = slot;
+        for (int r0 = rs; r0 < m; r0 += 64) Q.tiles.push_back(make_int4(s, r0, c0, slot++));
+        Q.diag.push_back(make_int4(s, c0, p0, slot - p0));
+      }
+      st.tile_cnt = (int)Q.tiles.size() - st.tile_off;
+      st.diag_cnt = (int)Q.diag.size() - st.diag_off;
+      Q.pmax = std::max<long long>(Q.pmax, slot);
+      Q.launches += 2 * (st.tile_cnt > 0) + 1;
+      sl.steps.push_back(st);
+    }
+  }
+}
+
+double selinv_flops(const CholPlan& P) {
+  double f = 0;
+  for (int s = 0; s < P.ns; s++)
+    for (int c0 = 0; c0 < P.w[s]; c0 += 64) {   // G, Z_Rb, G' Z_Rb, X'X per pivot block
+      const double nb = std::min(64, P.w[s] - c0), nr = P.m[s] - c0 - nb;
+      f += nr * nb * nb + 2.0 * nr * nr * nb + 2.0 * nr * nb * nb + nb * nb * nb / 3.0;
+    }
+  return f;
+}
+
+void selinv_edge_table(const CholPlan& P, const int2* pairs, long long ne, int4* out) {
+  const int nth = ne >= 4096 ? 16 : 1;
+  plan_parallel(nth, [&](int t) {
+    for (long long e = ne * t / nth; e < ne * (t + 1) / nth; e++) {
+      const int q1 = P.iperm[pairs[e].x], q2 = P.iperm[pairs[e].y];
+      const int a = std::min(q1, q2), b = std::max(q1, q2);   // a is eliminated first: b is a row of a's front
+      const int s = P.dg_front[a];
+      const int* r0 = P.rows.data() + P.rptr[s];
+      const int* r1 = P.rows.data() + P.rptr[s + 1];
+      const int* at = std::find(r0, r1, b);
+      // (a factor's poses always share the front of the earlier one; a miss
+      // would be a plan that does not cover the graph: flagged with front -1)
+      out[e] = at == r1 ? make_int4(-1, 0, 0, 0) : make_int4(s, 3 * (int)(at - r0), 3 * P.dg_loc[a], q1 < q2);
+    }
+  });
+}
+
 static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& slot_col) {
   static const bool timing = getenv("PGO_PLAN_TIMING") != nullptr;
   auto tlast = std::chrono::steady_clock::now();
@@ -1300,6 +1390,8 @@ static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const st
     P.schedule_error = P.schedule_error || out[L].schedule_error;
   }
   phase("schedule");
+  selinv_schedule(P);
+  phase("selinv");
   chol_assembly(P, row_ptr, slot_col);
   phase("assembly");
 }

@@ -246,8 +246,13 @@ class Marginals:
     def marginalCovariance(self, key):
         return self.marginalCovariances([key])[0]
 
-    def marginalCovariances(self, keys):
+    def marginalCovariances(self, keys=None):
+        """The given keys' covariances; with ``keys=None`` every key's, in the
+        Values' order, from one selected-inversion pass (the loop over all
+        keyframes of graph.cpp:121-131 as one call)."""
         with _build(self.graph, self.values, self.device) as pg:
+            if keys is None:
+                return pg.marginal_covariances_all()
             return pg.marginal_covariances(keys)
 
 

@@ -282,6 +282,21 @@ class PoseGraph:
         self._check(self._L.pgo_marginal_covariances(self._h, len(keys), L.u64ptr(keys), L.dptr(out)))
         return out
 
+    def marginal_covariances_all(self, edges=False):
+        """Every pose's 3x3 covariance in one selected-inversion pass, (n, 3, 3) in
+        insertion order: gtsam::Marginals once, then marginalCovariance(key) over
+        all keyframes (graph.cpp:120,126-127).  With edges=True also (E, 3, 3):
+        per between factor the block of H^-1 with k1's rows and k2's columns, so
+        [[cov[k1], X], [X.T, cov[k2]]] is the factor's joint marginal."""
+        n = self.num_vertices
+        cov = np.zeros((n, 3, 3))
+        if not edges:
+            self._check(self._L.pgo_marginal_covariances_all(self._h, L.dptr(cov) if n else None, None))
+            return cov
+        cross = np.zeros((self.num_factors - self._priors, 3, 3))   # (the between factors)
+        self._check(self._L.pgo_marginal_covariances_all(self._h, L.dptr(cov) if n else None, L.dptr(cross)))
+        return cov, cross
+
     def set_poses(self, xyt, keys=None):
         xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
         kp = None
@@ -406,6 +421,16 @@ class PoseGraph:
         lv = out[16:16 + 6 * nl].reshape(-1, 6)
         summary["levels_table"] = lv
         return summary
+
+    def debug_selinv_plan(self, cap=4096):
+        """Host-only summary of marginal_covariances_all's pass: launches,
+        algorithmic flops, doubles of extra device workspace, levels, and the
+        launches of each level (leaves first)."""
+        out = np.zeros(cap)
+        self._check(self._L.pgo_debug_selinv_plan(self._h, L.dptr(out), cap))
+        nl = int(out[3])
+        return {"launches": int(out[0]), "flops": float(out[1]), "workspace_doubles": float(out[2]), "levels": nl,
+                "level_launches": out[4:4 + nl].astype(np.int64)}
 
     def debug_fronts(self):
         """Host-only: (w, m, level) of every supernode of the Cholesky plan."""

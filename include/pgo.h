@@ -320,6 +320,23 @@ int pgo_error(pgo_graph *g, double *err);
    prior) returns PGO_E_INDETERMINANT, as GTSAM's Cholesky throws. */
 int pgo_marginal_covariances(pgo_graph *g, size_t n, const uint64_t *keys, double *out);
 
+/* gtsam::Marginals(graph, values) once, then marginalCovariance(key) for every
+   key (graph.cpp:120,126-127), in one pass: one undamped factorisation, then
+   the entries of H^-1 on the factor's pattern (the selected inverse) top-down
+   over the fronts -- about twice the factorisation's flops for all poses.
+   cov:  9 doubles per vertex, insertion order, row-major.  This is the vertex's
+         block of H^-1, the same definition as pgo_marginal_covariances: H at the
+         current values, undamped, the weighted H under a robust loss.
+   edge_cross (may be NULL): 9 doubles per between factor, insertion order.  It
+         is the block of H^-1 with the rows of k1 and the columns of k2,
+         row-major.  Together with cov[k1] and cov[k2] it is the factor's 6x6
+         joint marginal (a loop closure's Mahalanobis gate).
+   Singular H -> PGO_E_INDETERMINANT.
+   A factor on a key never inserted -> PGO_E_NO_KEY.
+   cov NULL with vertices present -> PGO_E_ARG.
+   A graph with no vertex -> PGO_OK. */
+int pgo_marginal_covariances_all(pgo_graph *g, double *cov, double *edge_cross);
+
 /* ---- loop-closure candidate search -----------------------
    The closest_keyframe service (graph.cpp:146-178): among the vertices in
    insertion order except the last `skip` (keyframes_to_skip_in_loop_closing,
@@ -460,6 +477,15 @@ int pgo_debug_solve(pgo_graph *g, double lambda, const pgo_params *params, doubl
  * their front's edge; from out[16], 6 per level (leaves first):
  * fronts, max m, max 64-blocks, panel steps, small fronts, syrk tiles. */
 int pgo_debug_plan(pgo_graph *g, double *out, int cap);
+
+/* Host-only: the selected-inversion pass of pgo_marginal_covariances_all as
+ * the plan of the graph as it stands schedules it (cap >= 4).  out[0] kernel
+ * launches of the pass (read-out included), out[1] its algorithmic flops,
+ * out[2] doubles of device workspace beside the factorisation's (Z in the
+ * fronts' layout, the panel scratch, the partial products, the read-out
+ * buffer; 0 would be an in-place pass), out[3] levels; from out[4] the
+ * launches of each level, leaves first. */
+int pgo_debug_selinv_plan(pgo_graph *g, double *out, int cap);
 /* Host-only: the subtree partition the PGO_MULTI_PARTITION factorisation
  * uses over `size` ranks: owner[s] per supernode (rank, -1 = top front;
  * returns the supernode count, arrays filled up to cap) and out[0..size+1] =

@@ -224,6 +224,7 @@ class Marginals {
     o.device = device;
     g_ = pgo_create(&o);
     if (!g_) throw std::runtime_error("pgo_create failed");
+    n_ = values.size();
     for (size_t i = 0; i < values.size(); i++) {
       const Pose2& p = values.poses()[i];
       throw_status(pgo_add_vertex(g_, values.keys()[i], p.x(), p.y(), p.raw_theta()), g_);
@@ -247,8 +248,19 @@ class Marginals {
     return out;
   }
 
+  // marginalCovariance(key) for every key, in the Values' order, from one
+  // factorisation and one selected-inversion pass (the loop over all
+  // keyframes of graph.cpp:121-131 as one call)
+  std::vector<Matrix3> marginalCovariances() const {
+    std::vector<Matrix3> out(n_);
+    static_assert(sizeof(Matrix3) == 9 * sizeof(double), "Matrix3 is nine packed doubles");
+    throw_status(pgo_marginal_covariances_all(g_, n_ ? out[0].m : nullptr, nullptr), g_);
+    return out;
+  }
+
  private:
   pgo_graph* g_ = nullptr;
+  size_t n_ = 0;
 };
 
 }  // namespace pgo_gtsam
