@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "pgo_chol.h"
+#include "pgo_lm.h"
 #include "pgo_structure.h"
 
 namespace {
@@ -723,9 +724,364 @@ int check_structure() {
   return 0;
 }
 
+// ---- the optimiser's control (pgo_lm.h) against GTSAM's loop, one try at a time ----
+
+struct ScriptTry {
+  double solved, new_e, lin_change;
+};
+
+// Scripted outcomes: try k of linearisation i, whatever lambda it runs at.
+// Past a linearisation's listed tries (and past the listed linearisations):
+// `rest`, a solved try that doubles the error.
+struct LmCase {
+  const char* name;
+  pgo_params p;
+  double err0 = 100.0;
+  std::vector<std::vector<ScriptTry>> lins;
+  std::vector<double> lin_err;   // per listed linearisation (the robust guard's scale); empty: the error
+  ScriptTry at(int i, int k) const {
+    if (i < (int)lins.size() && k < (int)lins[i].size()) return lins[i][k];
+    return {1.0, 2.0 * err0, 1.0};
+  }
+};
+
+struct RefRun {
+  std::vector<double> trace;   // 7 columns
+  int iters = 0, inner = 0, lins = 0, status = PGO_OK, stop_reason = PGO_STOP_CONVERGED;
+  double lam = 0, factor = 0, err = 0;
+  std::vector<int> tries;      // per linearisation: tries made
+  std::vector<int> accepted;   // per linearisation: the accepted try, -1 none
+};
+
+bool ref_converged(const pgo_params& p, double cur, double nw) {
+  if (nw <= p.error_tol) return true;
+  const double absd = cur - nw, reld = absd / cur;
+  return (p.relative_error_tol != 0.0 && reld <= p.relative_error_tol) || absd <= p.absolute_error_tol;
+}
+
+// LevenbergMarquardtOptimizer::iterate / tryLambda and NonlinearOptimizer::
+// defaultOptimize as the C oracle states them, sequentially; the stop reason
+// as include/pgo.h defines it.
+RefRun lm_reference(const LmCase& c) {
+  const pgo_params& prm = c.p;
+  RefRun R;
+  double err = c.err0, lam = prm.lambda_initial, factor = prm.lambda_factor;
+  int iters = 0, inner = 0, rc = PGO_OK, how = PGO_STOP_CONVERGED;
+  auto row = [&](double a, double b, double s, double lc, double e, double f, double acc) {
+    for (double v : {a, b, s, lc, e, f, acc}) R.trace.push_back(v);
+  };
+  if (!(err <= prm.error_tol) && iters < prm.max_iterations) {
+    double new_err = err;
+    for (;;) {
+      const double cur_err = new_err;
+      const int i = R.lins++;
+      R.tries.push_back(0);
+      R.accepted.push_back(-1);
+      if (prm.algorithm == PGO_ALG_GN) {
+        const ScriptTry s = c.at(i, R.tries[i]++);
+        if (s.solved == 0.0) {
+          rc = PGO_E_INDETERMINANT;
+          break;
+        }
+        R.accepted[i] = 0;
+        err = s.new_e;
+        iters++;
+        inner++;
+        row(iters, 0, 1, NAN, err, 0, 1);
+      } else {
+        for (;;) {  // tryLambda
+          double fidelity = 0.0, new_e = INFINITY, lin_change = NAN;
+          int success = 0, stop = 0;
+          const ScriptTry s = c.at(i, R.tries[i]++);
+          const int solved = s.solved == 1.0;
+          if (solved) {
+            const double old_lin = i < (int)c.lin_err.size() ? c.lin_err[i] : err;
+            lin_change = s.lin_change;
+            if (lin_change >= 0) {
+              new_e = s.new_e;
+              const double cost_change = err - new_e;
+              if (lin_change > 2.220446049250313e-16 * old_lin) {
+                fidelity = cost_change / lin_change;
+                success = fidelity > prm.min_model_fidelity;
+              }
+              if (std::fabs(cost_change) < prm.relative_error_tol * err) stop = 1;
+            }
+          }
+          row(iters, lam, solved, lin_change, new_e, fidelity, success);
+          if (success) {
+            if (prm.use_fixed_lambda_factor) lam /= prm.lambda_factor;
+            else {
+              const double q = 2.0 * fidelity - 1.0;
+              const double f = 1.0 - q * q * q;
+              lam *= f > 1.0 / 3.0 ? f : 1.0 / 3.0;
+              factor *= 2.0;
+            }
+            if (lam < prm.lambda_lower_bound) lam = prm.lambda_lower_bound;
+            R.accepted[i] = R.tries[i] - 1;
+            err = new_e;
+            iters++;
+            inner++;
+            how = PGO_STOP_CONVERGED;
+            break;
+          }
+          if (!stop) {
+            lam *= factor;
+            inner++;
+            if (!prm.use_fixed_lambda_factor) factor *= 2.0;
+            if (lam >= prm.lambda_upper_bound) {
+              how = PGO_STOP_LAMBDA_BOUND;
+              break;
+            }
+            continue;
+          }
+          how = PGO_STOP_SMALL_CHANGE;
+          break;
+        }
+      }
+      new_err = err;
+      if (prm.max_outer > 0 && R.lins >= prm.max_outer) {
+        how = PGO_STOP_MAX_OUTER;
+        break;
+      }
+      if (!(iters < prm.max_iterations && !ref_converged(prm, cur_err, new_err) && std::isfinite(cur_err))) break;
+    }
+  }
+  R.iters = iters, R.inner = inner, R.lam = lam, R.factor = factor, R.err = err;
+  R.status = rc != PGO_OK ? rc : (iters >= prm.max_iterations && prm.max_iterations > 0 ? PGO_W_MAXITER : PGO_OK);
+  R.stop_reason = rc < 0                                                       ? PGO_STOP_ERROR
+                  : how == PGO_STOP_MAX_OUTER || R.status != PGO_W_MAXITER ? how
+                                                                               : PGO_STOP_MAX_ITER;
+  return R;
+}
+
+// The lane rule written out (the comment at LmControl::round_lanes): lanes a
+// rank runs in a round, given the tries the previous linearisation walked and
+// those of this one walked so far.
+struct LaneRow {
+  int mode, prev_walked, walked, L, profiled, exchange, Lr;
+};
+const LaneRow kLaneTable[] = {
+    // mode 0: every round runs all lanes
+    {0, 0, 0, 3, 0, 0, 3}, {0, 1, 0, 3, 0, 0, 3}, {0, 4, 1, 8, 0, 0, 8}, {0, 2, 0, 3, 1, 0, 1},
+    // mode 1: the first linearisation and one after a first-try acceptance expect 1 try
+    {1, 0, 0, 3, 0, 0, 1}, {1, 0, 1, 3, 0, 0, 3}, {1, 1, 0, 3, 0, 0, 1}, {1, 1, 1, 3, 0, 0, 3}, {1, 1, 4, 3, 0, 0, 3},
+    // after k >= 2 tries: 2 expected, not k
+    {1, 2, 0, 3, 0, 0, 2}, {1, 5, 0, 3, 0, 0, 2}, {1, 5, 1, 3, 0, 0, 1}, {1, 5, 2, 3, 0, 0, 3}, {1, 5, 0, 1, 0, 0, 1},
+    {1, 7, 0, 8, 0, 0, 2}, {1, 7, 2, 8, 0, 0, 8},
+    // a profiled factorisation runs alone; ranks that exchange run every lane
+    {1, 5, 0, 3, 1, 0, 1}, {1, 5, 2, 3, 1, 0, 1}, {1, 0, 0, 3, 0, 1, 3}, {1, 5, 0, 3, 0, 1, 3}, {1, 5, 0, 3, 1, 1, 1},
+    // mode 2: the previous linearisation's count, all lanes first
+    {2, 0, 0, 3, 0, 0, 3}, {2, 1, 0, 3, 0, 0, 1}, {2, 3, 0, 4, 0, 0, 3}, {2, 3, 1, 4, 0, 0, 2}, {2, 3, 3, 4, 0, 0, 4},
+    {2, 6, 0, 4, 0, 0, 4}, {2, 3, 0, 4, 0, 1, 4},
+    // mode 3: mode 1's rule, all lanes first
+    {3, 0, 0, 3, 0, 0, 3}, {3, 1, 0, 3, 0, 0, 1}, {3, 4, 0, 3, 0, 0, 2}, {3, 4, 1, 3, 0, 0, 1}, {3, 4, 2, 3, 0, 0, 3},
+    {3, 0, 0, 3, 1, 0, 1},
+};
+
+pgo_params lm_params() {
+  pgo_params p;
+  std::memset(&p, 0, sizeof(p));
+  p.max_iterations = 100;
+  p.relative_error_tol = p.absolute_error_tol = 1e-5;
+  p.lambda_initial = 1e-5, p.lambda_factor = 10.0, p.lambda_upper_bound = 1e5;
+  p.min_model_fidelity = 1e-3;
+  p.use_fixed_lambda_factor = 1;
+  p.algorithm = PGO_ALG_LM;
+  return p;
+}
+
+std::vector<LmCase> lm_cases() {
+  const ScriptTry rej = {1.0, 200.0, 1.0}, bad = {0.0, 0.0, NAN};
+  // a step from `from` to `to` at model fidelity fid
+  auto acc = [](double from, double to, double fid = 1.0) { return ScriptTry{1.0, to, (from - to) / fid}; };
+  // a solved try that barely moves: not accepted, the small cost change stops the linearisation
+  auto still = [](double at) { return ScriptTry{1.0, at - at * 1e-9, 1.0}; };
+  std::vector<LmCase> cs;
+  auto add = [&](const char* name, std::vector<std::vector<ScriptTry>> lins) -> LmCase& {
+    cs.push_back({name, lm_params(), 100.0, std::move(lins), {}});
+    return cs.back();
+  };
+  // accepted at once; the last step both negligible and accepted, then converged
+  add("first try", {{acc(100, 50)}, {acc(50, 25)}, {acc(25, 25 * (1 - 1e-7))}});
+  {   // accepted at try k = 2 .. 10: past a round boundary at every T, past a whole rejected round at T = 8
+    std::vector<std::vector<ScriptTry>> lins;
+    for (int k = 2; k <= 10; k++) {
+      lins.emplace_back(k - 1, rej);
+      lins.back().push_back(acc(100 - 10 * (k - 2), 90 - 10 * (k - 2)));
+    }
+    lins.push_back({acc(10, 10 - 1e-7)});
+    // (linearisation k leaves lambda k - 2 decades higher: 1e31 by the last)
+    add("try k", lins).p.lambda_upper_bound = 1e300;
+  }
+  add("bad pivot", {{bad, bad, acc(100, 50)}, {rej, bad, acc(50, 49)}, {still(49)}});
+  add("model increase", {{{1.0, 50.0, -1.0}, acc(100, 60)}, {{1.0, 10.0, -1e-30}, rej, acc(60, 59.9999999)}});
+  {   // the guard eps * lin_err: a decrease under it with lin_err >> err (the error's own scale
+      // would let it through and accept), one over it with lin_err << err (the error's would block it)
+    LmCase& c = add("robust guard", {{{1.0, 50.0, 1e-11}, acc(100, 60)}, {{1.0, 59.0, 1e-15}}, {still(59)}});
+    c.lin_err = {1e6, 1e-3, 59.0};
+    c.p.min_model_fidelity = 1e-3;
+  }
+  add("small change", {{rej, {1.0, 100.0 * (1 - 1e-9), 1.0}}});
+  for (int n = 1; n <= 9; n++) {   // n rejections reach the bound exactly: mid-round, at k = T - 1, at k = T
+    LmCase& c = add("upper bound", {});
+    c.p.lambda_factor = 2.0;
+    c.p.lambda_upper_bound = 131072.0;
+    c.p.lambda_initial = std::ldexp(1.0, 17 - n);
+  }
+  {   // an acceptance after the bound's last try but one, then the bound again
+    LmCase& c = add("upper bound, accepted before", {{rej, rej, acc(100, 50)}});
+    c.p.lambda_factor = 2.0, c.p.lambda_upper_bound = 131072.0, c.p.lambda_initial = std::ldexp(1.0, 14);
+  }
+  add("lower bound", {{acc(100, 50)}, {acc(50, 25)}, {rej, acc(25, 12)}, {still(12)}}).p.lambda_lower_bound = 1e-6;
+  {   // the factor doubling: rejections and acceptances at fidelities on both sides of the 1/3 floor
+    LmCase& c = add("doubling factor", {{rej, rej, acc(100, 50, 0.7)}, {rej, acc(50, 40, 0.05)}, {acc(40, 30, 0.5)},
+                                        {rej, rej, rej, acc(30, 29, 0.999)}, {still(29)}});
+    c.p.use_fixed_lambda_factor = 0;
+    c.p.lambda_lower_bound = 1e-7;
+    c.p.lambda_upper_bound = 1e30;   // (the doubled factor reaches 1e5 within the rejections of the fourth linearisation)
+  }
+  add("max_outer", {{acc(100, 50)}, {rej, acc(50, 25)}, {acc(25, 12)}}).p.max_outer = 2;
+  add("max_outer, rejected", {{acc(100, 50)}}).p.max_outer = 2;
+  add("max_iterations", {{acc(100, 50)}, {rej, acc(50, 25)}, {acc(25, 12)}}).p.max_iterations = 2;
+  add("max_iterations 0", {{acc(100, 50)}}).p.max_iterations = 0;
+  {
+    LmCase& c = add("max_outer and max_iterations", {{acc(100, 50)}, {rej, rej, acc(50, 25)}, {acc(25, 12)}});
+    c.p.max_outer = 2, c.p.max_iterations = 2;
+  }
+  add("error_tol at entry", {{acc(100, 50)}}).p.error_tol = 1e3;
+  add("error_tol reached", {{acc(100, 50)}, {acc(50, 5)}, {acc(5, 1)}}).p.error_tol = 10.0;
+  {
+    LmCase& c = add("gn", {{acc(100, 50)}, {acc(50, 25)}, {acc(25, 25 - 1e-9)}});
+    c.p.algorithm = PGO_ALG_GN;
+  }
+  {   // a Gauss-Newton step takes whatever error it lands on: the loop ends on the non-finite one
+    LmCase& c = add("gn non-finite", {{acc(100, 50)}, {{1.0, NAN, NAN}}, {acc(50, 5)}, {acc(5, 1)}});
+    c.p.algorithm = PGO_ALG_GN;
+  }
+  {
+    LmCase& c = add("gn failed solve", {{acc(100, 50)}, {bad}, {acc(50, 5)}});
+    c.p.algorithm = PGO_ALG_GN;
+  }
+  {
+    LmCase& c = add("gn max_iterations", {{acc(100, 50)}, {acc(50, 25)}, {acc(25, 12)}});
+    c.p.algorithm = PGO_ALG_GN, c.p.max_iterations = 2;
+  }
+  return cs;
+}
+
+bool same_double(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
+
+int check_lm() {
+  for (const LaneRow& r : kLaneTable) {   // the lane rule on its own
+    pgo::LmControl c(lm_params(), 100.0, r.mode);
+    c.prev_walked = r.prev_walked, c.walked = r.walked;
+    if (c.round_lanes(r.L, r.profiled != 0, r.exchange != 0) != r.Lr) {
+      std::fprintf(stderr, "mode %d prev %d walked %d L %d profiled %d exchange %d: not %d lanes\n", r.mode,
+                   r.prev_walked, r.walked, r.L, r.profiled, r.exchange, r.Lr);
+      return fail("lm: the lane rule");
+    }
+  }
+  const int splits[][2] = {{1, 1}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {1, 4}, {2, 2}, {4, 1}, {1, 6},
+                           {2, 3}, {3, 2}, {6, 1}, {1, 8}, {2, 4}, {4, 2}, {8, 1}};
+  long long runs = 0, rejected = 0;
+  for (const LmCase& c : lm_cases()) {
+    const RefRun R = lm_reference(c);
+    // what the reference walked is what a device would have recorded; the rest is speculative
+    pgo::LmScript S;
+    S.lin_ptr.assign(1, 0);
+    for (int i = 0; i < R.lins; i++) {
+      for (int k = 0; k < R.tries[i]; k++) {
+        const ScriptTry s = c.at(i, k);
+        for (double v : {s.solved, s.new_e, s.lin_change}) S.tries.push_back(v);
+      }
+      S.lin_ptr.push_back(S.lin_ptr.back() + R.tries[i]);
+      if (!c.lin_err.empty()) S.lin_err.push_back(i < (int)c.lin_err.size() ? c.lin_err[i] : NAN);
+    }
+    for (size_t r = 0; r < R.trace.size() / 7; r++) rejected += R.trace[7 * r + 6] == 0.0;
+    for (const auto& pl : splits)
+      for (int mode = 0; mode < 4; mode++)
+        for (int every : {0, 1, 3}) {
+          const int P = pl[0], L = pl[1], T = P * L;
+          pgo_params p = c.p;
+          p.profile_every = every;
+          pgo::LmReplay rep;
+          const pgo::LmControl C = pgo::lm_replay(p, c.err0, mode, P, L, every, S, &rep);
+          // where the sequential loop's accepted tries fall: the accepting
+          // round resumed after `base` walked tries and holds try base + k at
+          // rank k / L, lane k % L
+          std::vector<int> want;
+          size_t w = 0;
+          bool based = true;
+          for (int i = 0; i < R.lins; i++) {
+            if (R.accepted[i] < 0) continue;
+            const int base = w < rep.winner_base.size() ? rep.winner_base[w] : -1;
+            w++;
+            const int k = R.accepted[i] - base;
+            based = based && base >= 0 && k >= 0 && k < T && (c.p.algorithm != PGO_ALG_GN || base == 0);
+            want.push_back(k / L);
+            want.push_back(k % L);
+          }
+          if (c.p.algorithm == PGO_ALG_GN) want.clear(), based = rep.winner_base.empty();
+          based = based && (c.p.algorithm == PGO_ALG_GN || w == rep.winner_base.size());
+          const bool same = C.trace.size() == R.trace.size() &&
+                            (R.trace.empty() || !std::memcmp(C.trace.data(), R.trace.data(), R.trace.size() * sizeof(double))) &&
+                            C.iters == R.iters && C.inner == R.inner && C.linearizations == R.lins &&
+                            same_double(C.lam, R.lam) && same_double(C.factor, R.factor) && same_double(C.err, R.err) &&
+                            C.status == R.status && C.stop_reason == R.stop_reason && !rep.exhausted &&
+                            rep.winners == want && based;
+          if (!same) {
+            std::fprintf(stderr,
+                         "lm case '%s' (lambda0 %g), %d ranks x %d lanes, adapt %d, profiled every %d:\n"
+                         "  control: %zu rows, iters %d inner %d lins %d lam %.17g factor %g err %.17g status %d stop %d "
+                         "rounds %d winners %zu%s\n"
+                         "  GTSAM  : %zu rows, iters %d inner %d lins %d lam %.17g factor %g err %.17g status %d stop %d "
+                         "winners %zu\n",
+                         c.name, c.p.lambda_initial, P, L, mode, every, C.trace.size() / 7, C.iters, C.inner,
+                         C.linearizations, C.lam, C.factor, C.err, C.status, C.stop_reason, rep.rounds,
+                         rep.winners.size() / 2, rep.exhausted ? " (script exhausted)" : "", R.trace.size() / 7, R.iters,
+                         R.inner, R.lins, R.lam, R.factor, R.err, R.status, R.stop_reason, want.size() / 2);
+            return fail("lm: the control differs from the sequential loop");
+          }
+          runs++;
+        }
+  }
+  // what the cases are there to reach
+  auto ref_of = [](const char* name, int nth = 0) {
+    for (const LmCase& c : lm_cases())
+      if (!std::strcmp(c.name, name) && nth-- == 0) return lm_reference(c);
+    return RefRun();
+  };
+  const RefRun guard = ref_of("robust guard"), outer2 = ref_of("max_outer and max_iterations"), tryk = ref_of("try k");
+  const std::pair<const char*, bool> reached[] = {
+      {"robust guard", guard.trace.size() >= 21 && guard.trace[6] == 0.0 && guard.trace[5] == 0.0 && guard.trace[14 + 6] == 1.0},
+      {"try k", tryk.iters == 10 && tryk.stop_reason == PGO_STOP_CONVERGED &&
+                    tryk.accepted == std::vector<int>{1, 2, 3, 4, 5, 6, 7, 8, 9, 0}},
+      {"small change", ref_of("small change").stop_reason == PGO_STOP_SMALL_CHANGE},
+      {"upper bound", ref_of("upper bound", 4).inner == 5 && ref_of("upper bound", 4).stop_reason == PGO_STOP_LAMBDA_BOUND},
+      {"lower bound", ref_of("lower bound").lam == 1e-6},
+      {"max_outer", ref_of("max_outer").stop_reason == PGO_STOP_MAX_OUTER},
+      {"max_iterations", ref_of("max_iterations").status == PGO_W_MAXITER && ref_of("max_iterations").stop_reason == PGO_STOP_MAX_ITER},
+      {"max_outer and max_iterations", outer2.status == PGO_W_MAXITER && outer2.stop_reason == PGO_STOP_MAX_OUTER},
+      {"error_tol at entry", ref_of("error_tol at entry").lins == 0},
+      {"max_iterations 0", ref_of("max_iterations 0").status == PGO_OK && ref_of("max_iterations 0").lins == 0},
+      {"gn non-finite", ref_of("gn non-finite").lins == 3},
+      {"gn failed solve", ref_of("gn failed solve").status == PGO_E_INDETERMINANT && ref_of("gn failed solve").stop_reason == PGO_STOP_ERROR},
+      {"doubling factor", ref_of("doubling factor").factor == 10.0 * 1024.0},
+  };
+  for (const auto& [name, ok] : reached)
+    if (!ok) {
+      std::fprintf(stderr, "lm case '%s'\n", name);
+      return fail("lm: a scripted case does not reach what it is there for");
+    }
+  std::printf("lm control: %lld runs against the sequential loop (%lld rejected tries per pass), lane rule ok\n", runs,
+              rejected);
+  return 0;
+}
+
 }  // namespace
 
 int main() {
+  if (check_lm()) return 1;
   if (check_structure()) return 1;
   for (int n : {1, 2, 5}) {   // graphs smaller than the planner's thread count
     const Pattern G = restrict_pattern(make_pattern(40, 0, 3), n);

@@ -26,6 +26,7 @@
 #include "pgo_comm.h"
 #include "pgo_search.h"
 #include "pgo_device.h"
+#include "pgo_lm.h"
 #include "pgo_structure.h"
 
 using pgo::DevGraph;
@@ -1110,8 +1111,8 @@ DevGraph lane_view(const pgo_graph* g, int l) {
 
 // nb >= 2 consecutive lambda tries in one batched factor + solve (captured
 // graph per lane count), then per lane: model decrease, retract, error; one
-// read-back.  out[4 l ..] = {solved, new error, delta'H delta, g'delta}.
-int run_lanes(pgo_graph* g, const pgo_params& p, int nb, const double* lams, double* out, pgo_stats* st) {
+// read-back.  out[l]: lane l's outcome.
+int run_lanes(pgo_graph* g, const pgo_params& p, int nb, const double* lams, pgo::TryOutcome* out, pgo_stats* st) {
   DevGraph& d = g->d;
   hipEvent_t* ev = g->ev;
   g->factorizations++;
@@ -1153,12 +1154,8 @@ int run_lanes(pgo_graph* g, const pgo_params& p, int nb, const double* lams, dou
       g->handoff_timeout = true;
       return fail(g, PGO_E_HIP, "factorisation: an in-launch hand-off timed out");
     }
-  for (int l = 0; l < nb; l++) {
-    out[4 * l] = flags[l] == 0 ? 1.0 : 0.0;
-    out[4 * l + 1] = g->h_lanes[4 * l];
-    out[4 * l + 2] = g->h_lanes[4 * l + 1];
-    out[4 * l + 3] = g->h_lanes[4 * l + 2];
-  }
+  for (int l = 0; l < nb; l++)
+    out[l] = {flags[l] == 0 ? 1.0 : 0.0, g->h_lanes[4 * l], g->h_lanes[4 * l + 1], g->h_lanes[4 * l + 2]};
   if (st) {
     st->ms_solve += ms_between(ev[2], ev[3]);
     st->ms_update += ms_between(ev[3], ev[4]);
@@ -1188,13 +1185,6 @@ double ms_between(hipEvent_t a, hipEvent_t b) {
     return 0.0;
   }
   return ms;
-}
-
-bool check_convergence(const pgo_params& p, double cur, double nw) {  // NonlinearOptimizer.cpp
-  if (nw <= p.error_tol) return true;
-  const double absd = cur - nw;
-  const double reld = absd / cur;
-  return (p.relative_error_tol != 0.0 && reld <= p.relative_error_tol) || absd <= p.absolute_error_tol;
 }
 
 }  // namespace
@@ -1614,12 +1604,6 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
   auto since_T0 = [&]() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
   };
-  // per-iteration record (pgo_get_trace): the oracle's trace columns + wall ms
-  auto trace_row = [&](double it, double lam_t, double solved, double lin_change, double new_e, double fid,
-                       double acc) {
-    const double row[kTraceCols] = {it, lam_t, solved, lin_change, new_e, fid, acc, since_T0()};
-    g->trace.insert(g->trace.end(), row, row + kTraceCols);
-  };
   g->last_upload = 0;
   int rc = ensure_device(g);
   if (rc != PGO_OK) return rc;
@@ -1635,9 +1619,6 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
     if (stats) *stats = st;
     return fail(g, PGO_E_NONFINITE, "initial error is not finite");
   }
-  double lam = p.lambda_initial, factor = p.lambda_factor;
-  int iters = 0, inner = 0;
-  int status = PGO_OK;
   if (p.algorithm == PGO_ALG_GN && g->gs.gauge_free && d.n > 0 && !(err <= p.error_tol)) {
     st.status = PGO_E_INDETERMINANT;
     if (stats) *stats = st;
@@ -1675,7 +1656,6 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
   double lin_err = err;
   // One lambda try (GTSAM tryLambda): solve (H + lam I) delta = -g, retract into
   // pose_cand, error there and the linear model decrease; one read-back.
-  // out = {solved, new error, delta'H delta, g'delta}.
   bool first_try = true;
   auto account_linearize = [&]() {   // after the first try of a linearisation has synchronised
     if (!first_try) return;
@@ -1687,7 +1667,7 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
     }
     first_try = false;
   };
-  auto run_try_once = [&](double lam_try, double* out) -> int {
+  auto run_try_once = [&](double lam_try, pgo::TryOutcome* out) -> int {
     SolveState ss;
     HIP_TRY(g, hipEventRecord(ev[2], d.stream));
     RC_TRY(linear_solve(g, p, lam_try, &st, &ss));
@@ -1705,10 +1685,7 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
     account_linearize();
     st.ms_solve += ms_between(ev[2], ev[3]);
     st.ms_update += ms_between(ev[3], ev[4]);
-    out[0] = ss.solved ? 1.0 : 0.0;
-    out[1] = g->h_scal[0];
-    out[2] = g->h_scal[1];
-    out[3] = g->h_scal[2];
+    *out = {ss.solved ? 1.0 : 0.0, g->h_scal[0], g->h_scal[1], g->h_scal[2]};
     return PGO_OK;
   };
   // a try whose in-launch hand-off timed out (a workgroup starved on a shared
@@ -1724,7 +1701,7 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
     }
     return rc;
   };
-  auto run_try = [&](double lam_try, double* out) -> int {
+  auto run_try = [&](double lam_try, pgo::TryOutcome* out) -> int {
     return retried([&] { return run_try_once(lam_try, out); });
   };
   pgo::Comm& cm = g->comm;
@@ -1743,94 +1720,69 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
   int L = 1;
   if (p.algorithm != PGO_ALG_GN && p.linear_solver != PGO_SOLVER_PCG && p.lambda_lanes > 1 && d.n > 0)
     L = ensure_lanes(g, p.lambda_lanes);
+  // an exchange between the ranks: its wall time into ms_comm, a failure under the call's name
+  auto comm_call = [&](const char* what, auto&& call) -> int {
+    const auto c0 = std::chrono::steady_clock::now();
+    std::string why;
+    const int rc = call(&why);
+    if (rc != PGO_OK) return fail(g, rc, std::string(what) + ": " + why);
+    st.ms_comm += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+    return PGO_OK;
+  };
   // every rank must agree on the lanes per rank (a lane allocation may fail on
   // one); a partitioned run's ranks factor the same lanes together (the
   // hybrid: the minimum over the group, then over the groups)
   auto agree_lanes = [&](pgo::Comm& c) -> int {
     std::vector<double> all(c.size);
     const double mineL = L;
-    std::string why;
-    const int rc = pgo::comm_allgather(&c, &mineL, 1, all.data(), d.stream, &why);
-    if (rc != PGO_OK) return fail(g, rc, "lane count all-gather: " + why);
+    RC_TRY(comm_call("lane count all-gather", [&](std::string* why) {
+      return pgo::comm_allgather(&c, &mineL, 1, all.data(), d.stream, why);
+    }));
     for (double v : all) L = std::min(L, (int)v);
     return PGO_OK;
   };
   if (partition && g->part_comm->size > 1) RC_TRY(agree_lanes(*g->part_comm));
   if (exchange && (!partition || hybrid)) RC_TRY(agree_lanes(cm));
   const int T = P * L;                       // tries per round
-  std::vector<double> lam_k(T), fac_k(T), outs(4 * T);
-  int last_outcome = PGO_STOP_CONVERGED;     // how the last linearisation's tries ended
-  std::vector<char> valid(T);
-  // Lanes sized to the tries expected, so the round that should reach the
-  // accepted try runs only the lanes up to it (a one-lane round is cheaper than
-  // a batched one); all lanes again if that try fails.  The expectation follows
-  // GTSAM's lambda dynamics: after a first-try acceptance lambda keeps falling
-  // and the next linearisation is expected to accept at once (1 try); after an
-  // acceptance that needed k >= 2 tries the next linearisation starts one decade
-  // below the accepted lambda, which just failed, so 2 tries are expected
-  // rather than k (C3: 13 rounds either way, two of them 2-lane instead of
-  // 3-lane).  The first linearisation of an optimize() expects 1: GTSAM starts
-  // at lambda = 1e-5, a nearly undamped step, which from odometry-initialised
-  // or warm-started values is accepted.  The tries and their order are
-  // unchanged (PGO_LANES_ADAPT=0: every round runs all lanes; 2: the previous
-  // linearisation's count, all lanes first; 3: this rule, all lanes first).
+  std::vector<pgo::TryOutcome> outs(T);
+  // the policy: which lambdas to try, how many lanes, what the outcomes mean (pgo_lm.h)
   static const int adapt_mode = getenv("PGO_LANES_ADAPT") ? atoi(getenv("PGO_LANES_ADAPT")) : 1;
-  static const bool adapt_lanes = adapt_mode != 0;
-  int prev_walked = 0;   // tries the previous linearisation walked (0: none yet)
-  if (!(err <= p.error_tol) && iters < p.max_iterations && d.n > 0) {
-    double new_err = err;
+  pgo::LmControl ctl(p, err, adapt_mode);
+  // per-iteration record (pgo_get_trace): the control's rows + wall ms
+  auto take_trace = [&]() {
+    for (size_t r = g->trace.size() / kTraceCols; r < ctl.trace.size() / pgo::kLmTraceCols; r++) {
+      const double* row = ctl.trace.data() + r * pgo::kLmTraceCols;
+      g->trace.insert(g->trace.end(), row, row + pgo::kLmTraceCols);
+      g->trace.push_back(since_T0());   // (a row's own stamp, as it is taken over)
+    }
+  };
+  if (ctl.start() && d.n > 0) {
     for (;;) {
-      const double cur_err = new_err;
       RoctxRange range_lin("linearisation");
       HIP_TRY(g, pgo::launch_linearize(d, ev[0], ev[1]));
       if (robust) HIP_TRY(g, pgo::launch_error_lin(d, d.pose, d.scal + 3));
       HIP_TRY(g, hipEventRecord(g->lin_done, d.stream));
-      st.linearizations++;
+      ctl.begin_linearization();
       first_try = true;
       if (p.algorithm == PGO_ALG_GN) {  // one plain step; every rank computes the same one
-        double o[4];
-        RC_TRY(run_try(0.0, o));
-        if (o[0] == 0.0) {
-          status = PGO_E_INDETERMINANT;
-          break;
-        }
-        std::swap(d.pose, d.pose_cand);
-        err = o[1];
-        iters++;
-        inner++;
-        trace_row(iters, 0.0, 1.0, NAN, err, 0.0, 1.0);
+        pgo::TryOutcome o;
+        RC_TRY(run_try(0.0, &o));
+        if (ctl.gn_step(o)) std::swap(d.pose, d.pose_cand);
+        take_trace();
       } else {
-        // Lambda rounds.  GTSAM tries lam_0 = lam, lam_{k+1} = lam_k * f_k (f_k
-        // doubling when the factor is not fixed) until one is accepted, the cost
-        // change is negligible, or lam_{k+1} reaches the upper bound.  Try k of a
-        // round runs on rank k / L, lane k % L; the outcomes are walked in
-        // sequence order with GTSAM's rules, so the accepted step is the
-        // sequential one.
-        int walked = 0;   // tries of this linearisation walked so far
+        // Lambda rounds: try k of a round runs on rank k / L, lane k % L
         for (;;) {
           RoctxRange range_round("lambda_round");
-          lam_k[0] = lam;
-          fac_k[0] = factor;
-          valid[0] = 1;
-          for (int k = 1; k < T; k++) {
-            lam_k[k] = lam_k[k - 1] * fac_k[k - 1];
-            fac_k[k] = p.use_fixed_lambda_factor ? fac_k[k - 1] : 2.0 * fac_k[k - 1];
-            valid[k] = valid[k - 1] && lam_k[k] < p.lambda_upper_bound;
-          }
-          // a profiled factorisation (lane 0, eager, timed launches) runs alone
+          ctl.plan_round(T);
           const bool prof_next = p.profile_every > 0 && (g->factorizations % p.profile_every) == 0;
-          int Lr = prof_next ? 1 : L;
-          const int expect = adapt_mode == 2 ? prev_walked : prev_walked == 0 ? (adapt_mode == 3 ? 0 : 1)
-                                                                              : std::min(prev_walked, 2);
-          if (adapt_lanes && !exchange && expect > walked) Lr = std::min(Lr, expect - walked);
-          std::vector<double> mine(4 * L, 0.0);
-          for (int l = 0; l < L; l++) mine[4 * l] = -1.0;  // -1: no try (past the bound / lane idle)
+          const int Lr = ctl.round_lanes(L, prof_next, exchange);
+          std::vector<pgo::TryOutcome> mine(L, pgo::kNoTry);   // (past the bound / lane idle: no try)
           int nb = 0;   // this rank's valid tries (a prefix of its lanes)
-          while (nb < Lr && valid[me * L + nb]) nb++;
+          while (nb < Lr && ctl.valid[me * L + nb]) nb++;
           if (nb == 1) {
-            RC_TRY(run_try(lam_k[me * L], &mine[0]));
+            RC_TRY(run_try(ctl.lam_k[me * L], &mine[0]));
           } else if (nb > 1) {
-            RC_TRY(retried([&] { return run_lanes(g, p, nb, &lam_k[me * L], mine.data(), &st); }));
+            RC_TRY(retried([&] { return run_lanes(g, p, nb, &ctl.lam_k[me * L], mine.data(), &st); }));
             st.solves += nb;
             account_linearize();
             if (robust) lin_err = g->h_lanes[3];
@@ -1840,114 +1792,42 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
           }
           st.lambda_rounds++;
           if (exchange) {
-            const auto c0 = std::chrono::steady_clock::now();
-            std::string why;
-            const int rc = pgo::comm_allgather(&cm, mine.data(), 4 * L, outs.data(), d.stream, &why);
-            if (rc != PGO_OK) return fail(g, rc, "lambda round all-gather: " + why);
-            st.ms_comm += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+            RC_TRY(comm_call("lambda round all-gather", [&](std::string* why) {
+              return pgo::comm_allgather(&cm, &mine[0].solved, 4 * L, &outs[0].solved, d.stream, why);
+            }));
           } else {
-            std::copy(mine.begin(), mine.end(), outs.begin());
+            outs = mine;
           }
-          // a lane that sat out a profiled round: its tries count as not made,
-          // the walk stops there and the next round resumes from it
-          for (int k = 0; k < T; k++)
-            if (outs[4 * k] == -1.0) {
-              for (int j = k; j < T; j++) valid[j] = 0;
-              break;
-            }
-          int winner = -1;
-          bool done = false;
-          double new_e = INFINITY;
-          for (int k = 0; k < T && valid[k]; k++) {
-            const double* o = &outs[4 * k];
-            double fidelity = 0.0, lin_change = NAN, try_e = INFINITY;
-            bool success = false, stop = false;
-            if (o[0] == 1.0) {
-              const double xhx = o[2], gx = o[3];
-              lin_change = -(gx + 0.5 * xhx);
-              if (lin_change >= 0) {
-                new_e = try_e = o[1];
-                const double cost_change = err - new_e;
-                if (lin_change > 2.220446049250313e-16 * (robust ? lin_err : err)) {
-                  fidelity = cost_change / lin_change;
-                  success = fidelity > p.min_model_fidelity;
-                }
-                if (std::fabs(cost_change) < p.relative_error_tol * err) stop = true;
-              }
-            }
-            trace_row(iters, lam_k[k], o[0], lin_change, try_e, fidelity, success ? 1.0 : 0.0);
-            walked++;
-            lam = lam_k[k];
-            factor = fac_k[k];
-            if (success) last_outcome = PGO_STOP_CONVERGED;
-            else if (stop) last_outcome = PGO_STOP_SMALL_CHANGE;
-            if (success) {  // decreaseLambda
-              if (p.use_fixed_lambda_factor) {
-                lam /= p.lambda_factor;
-              } else {
-                const double q = 2.0 * fidelity - 1.0;
-                lam *= std::max(1.0 / 3.0, 1.0 - q * q * q);
-                factor *= 2.0;
-              }
-              lam = std::max(p.lambda_lower_bound, lam);
-              winner = k;
-              done = true;
-              break;
-            }
-            if (stop) {
-              done = true;
-              break;
-            }
-            lam *= factor;  // increaseLambda
-            inner++;
-            if (!p.use_fixed_lambda_factor) factor *= 2.0;
-            if (lam >= p.lambda_upper_bound) {
-              last_outcome = PGO_STOP_LAMBDA_BOUND;
-              done = true;
-              break;
-            }
-          }
-          if (winner >= 0) {
-            const int wr = winner / L, wl = winner % L;
+          const pgo::LmWalk w = ctl.walk(outs.data(), robust ? lin_err : ctl.err);
+          take_trace();
+          if (w.winner >= 0) {
+            const int wr = w.winner / L, wl = w.winner % L;
             // the accepted candidate values: lane wl's buffer on rank wr
             double4** cand = wr == me && wl > 0 ? &g->lanes[wl - 1].pose_cand : &d.pose_cand;
-            if (exchange) {
-              const auto c0 = std::chrono::steady_clock::now();
-              std::string why;
-              const int rc = pgo::comm_broadcast_device(&cm, *cand, sizeof(double4) * (size_t)d.n, wr, d.stream, &why);
-              if (rc != PGO_OK) return fail(g, rc, "accepted values broadcast: " + why);
-              st.ms_comm += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
-            }
+            if (exchange)
+              RC_TRY(comm_call("accepted values broadcast", [&](std::string* why) {
+                return pgo::comm_broadcast_device(&cm, *cand, sizeof(double4) * (size_t)d.n, wr, d.stream, why);
+              }));
             std::swap(d.pose, *cand);
-            err = new_e;
-            iters++;
-            inner++;
           }
-          if (done) break;
+          if (w.done) break;
         }
-        prev_walked = walked;
       }
-      if (status != PGO_OK) break;
-      new_err = err;
-      if (p.max_outer > 0 && st.linearizations >= p.max_outer) {
-        last_outcome = PGO_STOP_MAX_OUTER;
-        break;
-      }
-      if (!(iters < p.max_iterations && !check_convergence(p, cur_err, new_err) && std::isfinite(cur_err))) break;
+      if (!ctl.next_linearization()) break;
     }
   }
-  if (status == PGO_OK && iters >= p.max_iterations && p.max_iterations > 0) status = PGO_W_MAXITER;
-  st.stop_reason = status < 0 ? PGO_STOP_ERROR
-                   : (status == PGO_W_MAXITER && last_outcome != PGO_STOP_MAX_OUTER ? PGO_STOP_MAX_ITER : last_outcome);
+  ctl.finish();
   g->host_values = false;
-  st.status = status;
-  st.iterations = iters;
-  st.inner_iterations = inner;
-  st.final_error = err;
+  st.status = ctl.status;
+  st.stop_reason = ctl.stop_reason;
+  st.linearizations = ctl.linearizations;
+  st.iterations = ctl.iters;
+  st.inner_iterations = ctl.inner;
+  st.final_error = ctl.err;
   st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count();
   if (stats) *stats = st;
-  if (status < 0) return fail(g, status, pgo_status_string(status));
-  return status;
+  if (ctl.status < 0) return fail(g, ctl.status, pgo_status_string(ctl.status));
+  return ctl.status;
 }
 
 int pgo_closest_keyframe(pgo_graph* g, double x, double y, int skip, uint64_t* key, double* dist) {

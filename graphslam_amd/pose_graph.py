@@ -68,6 +68,46 @@ def default_params(**kw) -> L.PgoParams:
     return p
 
 
+def trace_linearisations(trace, gn=False):
+    """A trace's tries (solved, candidate error, model decrease) split where
+    the optimiser linearised again: after every accepted try (a linearisation
+    without one is the last); Gauss-Newton: every step."""
+    trace = np.asarray(trace)
+    tries = trace[:, [2, 4, 3]]
+    if gn or not len(tries):
+        return [tries[i:i + 1] for i in range(len(tries))]
+    cuts = list(np.nonzero(trace[:, 6] == 1)[0] + 1)
+    if not cuts or cuts[-1] != len(trace):
+        cuts.append(len(trace))
+    return [tries[a:b] for a, b in zip([0] + cuts[:-1], cuts)]
+
+
+def debug_lm_replay(lins, initial_error, ranks=1, lanes=1, lin_err=None, adapt_mode=1, params=None, **kw):
+    """Host-only (pgo_debug_lm_replay): the optimiser's control driven as
+    pgo_optimize drives it over ranks x lanes tries per round, on recorded
+    tries instead of a device.  ``lins``: per linearisation an (n, 3) array of
+    (solved, error at the candidate, model decrease) -- a trace's columns 2,
+    4, 3.  Returns the seven-column trace, the counters and the (rank, lane)
+    of every accepted try."""
+    p = params if params is not None else default_params(**kw)
+    lins = [np.asarray(t, dtype=np.float64).reshape(-1, 3) for t in lins]
+    ptr = np.cumsum([0] + [len(t) for t in lins]).astype(np.int32)
+    tries = np.ascontiguousarray(np.concatenate(lins) if lins else np.zeros((0, 3)))
+    le = None if lin_err is None else np.ascontiguousarray(lin_err, dtype=np.float64)
+    cap = 8 * (len(tries) + len(lins) + 1)
+    trace, out = np.zeros((cap, 7)), np.zeros(11 + 2 * cap)
+    n = L.lib().pgo_debug_lm_replay(C.byref(p), float(initial_error), int(ranks), int(lanes), int(adapt_mode),
+                                    len(lins), ptr.ctypes.data_as(C.POINTER(C.c_int)), L.dptr(tries), L.dptr(le),
+                                    L.dptr(trace), cap, L.dptr(out), len(out))
+    if n < 0 or n > cap:
+        raise ValueError(f"pgo_debug_lm_replay: {n}")
+    names = ("iterations", "inner_iterations", "linearizations", "status", "stop_reason")
+    res = {k: int(out[i]) for i, k in enumerate(names)}
+    res.update(lam=out[5], factor=out[6], final_error=out[7], lambda_rounds=int(out[8]), exhausted=bool(out[9]),
+               trace=trace[:n].copy(), winners=out[11:11 + 2 * int(out[10])].astype(int).reshape(-1, 2))
+    return res
+
+
 class PoseGraph:
     """One pgo_graph handle (one HIP stream, graph + values resident in HBM)."""
 

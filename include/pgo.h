@@ -486,6 +486,26 @@ int pgo_debug_plan(pgo_graph *g, double *out, int cap);
  * buffer; 0 would be an in-place pass), out[3] levels; from out[4] the
  * launches of each level, leaves first. */
 int pgo_debug_selinv_plan(pgo_graph *g, double *out, int cap);
+/* Host-only, no handle: the optimiser's control (the lambda sequence, the
+ * accept / stop rules, the lane rule, the counters) driven as pgo_optimize
+ * drives it over `ranks` x `lanes` tries per round, on recorded tries instead
+ * of a device.  Linearisation i holds the tries [lin_ptr[i], lin_ptr[i + 1])
+ * of `tries`, 3 doubles each: solved (1/0), error at the candidate, linear
+ * model decrease (the trace's columns 2, 4, 3); lin_err (NULL: the error
+ * itself) is the linearised error per linearisation that the guard against a
+ * vanishing model decrease compares with.  A try past the recorded ones of
+ * its linearisation is speculative: its outcome is a poison that would be
+ * accepted if the control ever walked it.  adapt_mode: PGO_LANES_ADAPT;
+ * params->profile_every > 0: every such factorisation runs one lane alone.
+ * Returns the trace's row count and writes up to trace_cap rows of 7 doubles
+ * (pgo_get_trace's without the wall ms).  out (out_cap >= 11): iterations,
+ * inner iterations, linearisations, status, stop reason, final lambda, lambda
+ * factor and error, lambda rounds, 1 if the control asked for a linearisation
+ * past the recorded ones, accepted tries; then (rank, lane) of each accepted
+ * try as out_cap allows. */
+int pgo_debug_lm_replay(const pgo_params *params, double initial_error, int ranks, int lanes,
+                        int adapt_mode, int n_lin, const int *lin_ptr, const double *tries,
+                        const double *lin_err, double *trace, int trace_cap, double *out, int out_cap);
 /* Host-only: the subtree partition the PGO_MULTI_PARTITION factorisation
  * uses over `size` ranks: owner[s] per supernode (rank, -1 = top front;
  * returns the supernode count, arrays filled up to cap) and out[0..size+1] =

@@ -202,6 +202,34 @@ def test_trace_matches_oracle_c1nn(pg_cls, oracle_lib):
         assert tr[tr[:, 6] == 1].shape[0] == st["iterations"]
 
 
+@pytest.mark.parametrize("kw", [{}, {"lambda_initial": 1e-9}], ids=["defaults", "rejections"])
+def test_lm_replay_reproduces_optimize_c2(pg_cls, kw):
+    """The host-only replay of the optimiser's control (pgo_debug_lm_replay,
+    tests/test_lm_control.py) is what pgo_optimize really does: C2 optimised
+    with 1 and 3 lambda lanes, each trace's outcomes fed back to the replay at
+    1 and 3 lanes, gives the GPU's own rows (without the wall ms) bit for bit,
+    its counters, and -- at the lanes it ran with -- its lambda rounds.
+    (lambda_initial 1e-9: four tries of C2 are rejected, so the lanes matter.)"""
+    from graphslam_amd.pose_graph import debug_lm_replay, trace_linearisations
+    adapt = int(os.environ.get("PGO_LANES_ADAPT", "1"))
+    g = datasets.make("C2")
+    rejected = 0
+    for run_lanes in (1, 3):
+        pg = pg_cls.from_dataset(g)
+        st = pg.optimize(lambda_lanes=run_lanes, **kw)
+        tr = pg.trace()
+        rejected += int((tr[:, 6] == 0).sum())
+        for lanes in (1, 3):
+            r = debug_lm_replay(trace_linearisations(tr), st["initial_error"], 1, lanes, adapt_mode=adapt, **kw)
+            assert not r["exhausted"]
+            assert r["trace"].tobytes() == np.ascontiguousarray(tr[:, :7]).tobytes(), (run_lanes, lanes)
+            for k in ("iterations", "inner_iterations", "linearizations", "status", "stop_reason", "final_error"):
+                assert r[k] == st[k], (k, run_lanes, lanes)
+            if lanes == run_lanes:
+                assert r["lambda_rounds"] == st["lambda_rounds"], (run_lanes, lanes)
+    assert rejected > 0 or not kw
+
+
 def test_stop_reason(pg_cls):
     """pgo_stats.stop_reason tells apart what GTSAM reports as convergence."""
     g = datasets.make("C1")

@@ -13,7 +13,11 @@
   the delta's copy ranges replayed on a device copy; refused appends leaving
   the structure untouched; the owner-bit transitions (bind, append, incremental
   bind, unbind, changed order) against a full bind of a rebuild; the packing
-  of measurements and information.
+  of measurements and information.  And the optimiser's control (pgo_lm.cpp):
+  scripted lambda tries batched over ranks x lanes, adapt modes and profiled
+  rounds against a sequential transcription of GTSAM's loop (trace rows, lambda
+  and counters bitwise, stop reason, each winner's rank and lane; speculative
+  tries poisoned), and the lane rule as a table.
 * libpgo.so carries roctx ranges (pgo_optimize > plan / linearisation >
   lambda_round) for rocprofv3 --marker-trace.
 """
