@@ -88,6 +88,15 @@ class PgoStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved"}
 
 
+class PgoInitStats(C.Structure):
+    _fields_ = [("status", C.c_int), ("components", C.c_int), ("tree_depth", C.c_int), ("wraps", C.c_longlong),
+                ("error_before", C.c_double), ("error_after", C.c_double), ("ms_total", C.c_double),
+                ("ms_tree", C.c_double), ("ms_orient", C.c_double), ("ms_trans", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
 BROADCAST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 
@@ -168,6 +177,10 @@ def lib():
         "pgo_marginal_covariances": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_uint64), dp]),
         "pgo_marginal_covariances_all": (C.c_int, [vp, dp, dp]),
         "pgo_debug_selinv_plan": (C.c_int, [vp, dp, C.c_int]),
+        "pgo_initialize_linear": (C.c_int, [vp, C.POINTER(PgoInitStats)]),
+        "pgo_debug_init_tree": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                          C.c_size_t, C.c_size_t, C.c_size_t]),
+        "pgo_debug_init_system": (C.c_int, [vp, C.c_int, dp, dp, dp]),
         "pgo_debug_lm_replay": (C.c_int, [C.POINTER(PgoParams), C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_int), dp, dp, dp, C.c_int, dp, C.c_int]),
         "pgo_debug_fronts": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),

@@ -26,6 +26,7 @@
 #include "pgo_comm.h"
 #include "pgo_search.h"
 #include "pgo_device.h"
+#include "pgo_init.h"
 #include "pgo_lm.h"
 #include "pgo_structure.h"
 
@@ -149,6 +150,9 @@ struct pgo_graph {
   size_t sb_cap = 0, sbp_cap = 0;
   hipEvent_t sev_scan[2] = {}, sev_batch[2] = {};
   bool scan_timed = false, batch_timed = false;
+  // ---- linear initialisation (pgo_initialize_linear) ----
+  double* init_tgt = nullptr;               // [ne + np] the stages' angle targets, device factor / prior order
+  size_t init_tgt_cap = 0;
 };
 
 namespace {
@@ -1277,7 +1281,7 @@ void pgo_destroy(pgo_graph* g) {
     for (auto& e : g->fev)
       if (e) (void)hipEventDestroy(e);
     if (g->lin_done) (void)hipEventDestroy(g->lin_done);
-    void* sp[] = {g->s_d, g->s_i, g->sb_d, g->sb_i, g->sb_q, g->sbp_d, g->sbp_i};
+    void* sp[] = {g->s_d, g->s_i, g->sb_d, g->sb_i, g->sb_q, g->sbp_d, g->sbp_i, g->init_tgt};
     for (void* q : sp)
       if (q) (void)hipFree(q);
     for (hipEvent_t e : {g->sev_scan[0], g->sev_scan[1], g->sev_batch[0], g->sev_batch[1]})
@@ -1584,6 +1588,190 @@ int pgo_error(pgo_graph* g, double* err) {
   if (!g || !err) return PGO_E_ARG;
   RC_TRY(ensure_device(g));
   return device_error(g, g->d.pose, err);
+}
+
+// ---- linear initialisation (pgo_init.h / pgo_init.hip; DESIGN.md "Linear initialisation")
+
+// The host tree of the graph as it stands (keys resolved; no device).
+static int init_host_tree(pgo_graph* g, pgo::InitTree& T) {
+  pgo::PhaseTimer phase("init_host_tree");
+  std::vector<int2> eij;
+  RC_TRY(resolve_edges(g, 0, eij));
+  phase("resolve");
+  const size_t ne = eij.size(), np = g->pk.size();
+  std::vector<int> pv(np);
+  for (size_t q = 0; q < np; q++) {
+    auto a = g->index.find(g->pk[q]);
+    if (a == g->index.end())
+      return fail(g, PGO_E_NO_KEY, "prior factor on key " + std::to_string(g->pk[q]) + " with no inserted value");
+    pv[q] = a->second;
+  }
+  static_assert(sizeof(int2) == 2 * sizeof(int), "int2 is two packed ints");
+  const bool ok = pgo::init_tree((int)g->keys.size(), ne, reinterpret_cast<const int*>(eij.data()),
+                                 ne ? g->ez.data() + 2 : nullptr, 3, np, pv.data(), np ? g->pz.data() + 2 : nullptr, 3,
+                                 &T);
+  phase("tree");
+  if (!ok)
+    return fail(g, PGO_E_INDETERMINANT, "linear initialisation: the connected component of key " +
+                                            std::to_string(g->keys[T.free_vertex]) + " has no prior");
+  return PGO_OK;
+}
+
+// delta_e + 2 pi k_e per device factor, then theta_q + 2 pi k_q per device prior
+static int init_upload_targets(pgo_graph* g, const pgo::InitTree& T) {
+  constexpr double kTwoPi = 6.283185307179586476925286766559;
+  const pgo::GraphStructure& S = g->gs;
+  const size_t ne = (size_t)S.ne(), np = S.pv.size();
+  if (g->init_tgt_cap < ne + np) {
+    HIP_TRY(g, hipStreamSynchronize(g->d.stream));
+    if (g->init_tgt) (void)hipFree(g->init_tgt);
+    g->init_tgt = nullptr;
+    g->init_tgt_cap = 0;
+    const size_t cap = std::max(ne + np, g->cap_ne + np);
+    RC_TRY(dev_alloc(g, &g->init_tgt, cap));
+    g->init_tgt_cap = cap;
+  }
+  std::vector<double> h(ne + np);
+  for (size_t k = 0; k < ne; k++) {
+    const int e = S.dorder[k];
+    h[k] = T.delta[e] + kTwoPi * (double)T.k_edge[e];
+  }
+  for (size_t t = 0; t < np; t++) {
+    const int q = S.porder[t];
+    h[ne + t] = pgo::init_wrap(g->pz[3 * (size_t)q + 2]) + kTwoPi * (double)T.k_prior[q];
+  }
+  RC_TRY(h2d(g, g->init_tgt, h.data(), h.size()));
+  HIP_TRY(g, hipStreamSynchronize(g->d.stream));   // (the source is a local)
+  return PGO_OK;
+}
+
+// x = A^-1 b of the system in (d.D, d.V, d.g), undamped, eager launches; the
+// stream is drained and the pivot flag read.  A hand-off that timed out (a
+// workgroup starved on a time-sliced GPU) is reported as finish_solve reports
+// it, never re-run unseen: the values stay as they were.
+static int init_factor_solve(pgo_graph* g, const char* what) {
+  DevGraph& d = g->d;
+  *g->h_lam = 0.0;
+  HIP_TRY(g, hipMemcpyAsync(g->chol.d_lambda, g->h_lam, sizeof(double), hipMemcpyHostToDevice, d.stream));
+  HIP_TRY(g, pgo::chol_factor(g->chol, d.D, d.V, d.g, 1.0, d.stream, nullptr));
+  HIP_TRY(g, pgo::chol_solve(g->chol, d.x, d.stream));
+  int flag = 0;
+  HIP_TRY(g, hipMemcpyAsync(&flag, g->chol.d_flag, sizeof(int), hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(g, hipStreamSynchronize(d.stream));
+  if (flag & 2) {
+    g->handoff_timeout = true;
+    return fail(g, PGO_E_HIP, "factorisation: an in-launch hand-off timed out");
+  }
+  if (flag)
+    return fail(g, PGO_E_INDETERMINANT, std::string("linear initialisation: the ") + what +
+                                            " system is not positive definite");
+  return PGO_OK;
+}
+
+int pgo_initialize_linear(pgo_graph* g, pgo_init_stats* stats) {
+  if (!g) return PGO_E_ARG;
+  pgo_init_stats st;
+  std::memset(&st, 0, sizeof(st));
+  const auto T0 = std::chrono::steady_clock::now();
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+  };
+  auto done = [&](int rc) {
+    st.status = rc;
+    st.ms_total = ms_since(T0);
+    if (stats) *stats = st;
+    return rc;
+  };
+  if (g->keys.empty()) return done(PGO_OK);
+  // the tree first: a component without a prior is reported before any device work
+  pgo::InitTree T;
+  int rc = init_host_tree(g, T);
+  st.ms_tree = ms_since(T0);
+  if (rc != PGO_OK) return done(rc);
+  st.components = T.components;
+  st.tree_depth = T.tree_depth;
+  st.wraps = T.wraps;
+  if ((rc = ensure_device(g)) != PGO_OK) return done(rc);
+  DevGraph& d = g->d;
+  auto run = [&]() -> int {
+    HIP_TRY(g, hipSetDevice(g->device));
+    g->part_size = 1;   // every rank solves the whole system: a one-rank plan
+    RC_TRY(ensure_chol(g));
+    d.write_all = 0;
+    RC_TRY(device_error(g, d.pose, &st.error_before));
+    RC_TRY(init_upload_targets(g, T));
+    // the result is built in pose_cand and copied over the values at the end:
+    // a failed solve leaves them as they were
+    auto t = std::chrono::steady_clock::now();
+    HIP_TRY(g, pgo::launch_init_orient(d, g->init_tgt, g->init_tgt + d.ne));
+    RC_TRY(init_factor_solve(g, "orientation"));
+    HIP_TRY(g, pgo::launch_init_write_orient(d, d.x, d.pose_cand));
+    st.ms_orient = ms_since(t);
+    t = std::chrono::steady_clock::now();
+    HIP_TRY(g, pgo::launch_init_trans(d, d.pose_cand));
+    RC_TRY(init_factor_solve(g, "position"));
+    HIP_TRY(g, pgo::launch_init_write_trans(d, d.x, d.pose_cand));
+    HIP_TRY(g, hipStreamSynchronize(d.stream));
+    st.ms_trans = ms_since(t);
+    RC_TRY(device_error(g, d.pose_cand, &st.error_after));
+    if (!std::isfinite(st.error_after)) return fail(g, PGO_E_NONFINITE, "linear initialisation: non-finite result");
+    HIP_TRY(g, hipMemcpyAsync(d.pose, d.pose_cand, d.n * sizeof(double4), hipMemcpyDeviceToDevice, d.stream));
+    HIP_TRY(g, hipStreamSynchronize(d.stream));
+    g->dev_values = true;
+    g->host_values = false;
+    return PGO_OK;
+  };
+  return done(run());
+}
+
+int pgo_debug_init_tree(pgo_graph* g, int* parent, long long* k_edge, long long* k_prior, size_t cap_v, size_t cap_e,
+                        size_t cap_p) {
+  if (!g || (cap_v && !parent) || (cap_e && !k_edge) || (cap_p && !k_prior)) return PGO_E_ARG;
+  pgo::InitTree T;
+  RC_TRY(init_host_tree(g, T));
+  for (size_t v = 0; v < T.parent.size() && v < cap_v; v++) parent[v] = T.parent[v];
+  for (size_t e = 0; e < T.k_edge.size() && e < cap_e; e++) k_edge[e] = T.k_edge[e];
+  for (size_t q = 0; q < T.k_prior.size() && q < cap_p; q++) k_prior[q] = T.k_prior[q];
+  return (int)g->keys.size();
+}
+
+int pgo_debug_init_system(pgo_graph* g, int stage, double* hdiag, double* hoff, double* rhs) {
+  if (!g || (stage != 1 && stage != 2)) return PGO_E_ARG;
+  if (g->keys.empty()) return PGO_OK;
+  pgo::InitTree T;
+  RC_TRY(init_host_tree(g, T));
+  RC_TRY(ensure_device(g));
+  HIP_TRY(g, hipSetDevice(g->device));
+  DevGraph& d = g->d;
+  g->part_size = 1;
+  RC_TRY(ensure_chol(g));   // (the owner bits the sweeps write by)
+  d.write_all = 0;
+  if (stage == 1) {
+    RC_TRY(init_upload_targets(g, T));
+    HIP_TRY(g, pgo::launch_init_orient(d, g->init_tgt, g->init_tgt + d.ne));
+  } else {
+    HIP_TRY(g, pgo::launch_init_trans(d, d.pose));
+  }
+  std::vector<double> V(9 * (size_t)d.ne), D(6 * (size_t)d.n), G(3 * (size_t)d.n);
+  if (d.ne) HIP_TRY(g, hipMemcpyAsync(V.data(), d.V, V.size() * 8, hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(g, hipMemcpyAsync(D.data(), d.D, D.size() * 8, hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(g, hipMemcpyAsync(G.data(), d.g, G.size() * 8, hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(g, hipStreamSynchronize(d.stream));
+  if (hdiag)
+    for (int i = 0; i < d.n; i++) {
+      const double* s = &D[6 * (size_t)i];
+      double* o = hdiag + 9 * (size_t)i;
+      o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+      o[3] = s[1]; o[4] = s[3]; o[5] = s[4];
+      o[6] = s[2]; o[7] = s[4]; o[8] = s[5];
+    }
+  if (hoff)   // (both stages' blocks are symmetric: the owner's orientation does not matter)
+    for (int e = 0; e < d.ne; e++) {
+      const size_t de = (size_t)(g->gs.codes()[g->gs.edge_slot0[e]] >> 2);
+      std::memcpy(hoff + 9 * (size_t)e, &V[9 * de], 9 * sizeof(double));
+    }
+  if (rhs) std::memcpy(rhs, G.data(), G.size() * 8);
+  return PGO_OK;
 }
 
 int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {

@@ -105,4 +105,14 @@ hipError_t launch_pcg_vec(const DevGraph& d, int k, double tol2);
 hipError_t launch_model_decrease(const DevGraph& d, const double* delta, double* out2);
 hipError_t launch_spmv(const DevGraph& d, double lambda, const double* x, double* y);
 
+// Linear initialisation (pgo_init.hip): each stage's system in the Cholesky-mode
+// layout (d.D, owner records d.V[9 e + q], right-hand side d.g; the slot codes
+// must be bound to a plan).  tgt: delta_e + 2 pi k_e per device factor; ptgt:
+// theta_q + 2 pi k_q per device prior; stage 2 reads the (c, s) of `pose`.
+hipError_t launch_init_orient(const DevGraph& d, const double* tgt, const double* ptgt);
+hipError_t launch_init_trans(const DevGraph& d, const double4* pose);
+// the solutions (3 per vertex) into out: (0, 0, cos, sin) of the theta slot; the (x, y) slots
+hipError_t launch_init_write_orient(const DevGraph& d, const double* x, double4* out);
+hipError_t launch_init_write_trans(const DevGraph& d, const double* x, double4* out);
+
 }  // namespace pgo

@@ -256,6 +256,32 @@ class Marginals:
             return pg.marginal_covariances(keys)
 
 
+class lago:  # noqa: N801 -- mirrors gtsam::lago
+    """``gtsam::lago::initialize(graph, values)``: linear initial values for LM."""
+
+    @staticmethod
+    def initialize(graph: NonlinearFactorGraph, values: "Values", device=0) -> "Values":
+        """Two linear solves on the device (``PoseGraph.initialize_linear``):
+        orientations, then positions with the orientations held.  ``values``
+        only names the keys, as in GTSAM's two-argument form; its poses are
+        not used.  Returns new Values in the same key order.
+
+        Deviations from GTSAM's ``lago``: the spanning tree is breadth-first
+        from each component's first vertex with a prior (GTSAM: the odometric
+        path, or a minimum spanning tree); stage 2 applies no orientation
+        correction; the graph's priors are used as given (GTSAM adds an
+        anchor), so every connected component needs one
+        (IndeterminantLinearSystemException otherwise).  Robust noise models
+        are treated as their Gaussian part.  Parity with GTSAM is unpinned."""
+        with _build(graph, values, device) as pg:
+            pg.initialize_linear()
+            xyt = pg.poses()
+        out = Values()
+        for k, p in zip(values.keys(), xyt):
+            out.insert(k, Pose2(*p))
+        return out
+
+
 class LevenbergMarquardtParams:
     """gtsam::LevenbergMarquardtParams with GTSAM 4.0 defaults (+ PCG knobs)."""
 

@@ -229,6 +229,49 @@ class PoseGraph:
         self._check(rc)
         return self.last_stats
 
+    def initialize_linear(self):
+        """Two-stage linear initialisation (pgo_initialize_linear): the
+        orientations as one linear least-squares problem, the 2 pi ambiguities
+        fixed along a breadth-first spanning tree from each component's first
+        vertex with a prior, then the positions as a second one with the
+        orientations held.  Replaces the handle's values (which are not an
+        input) and returns the pgo_init_stats as a dict; a following
+        ``optimize()`` starts from the result.
+
+        Not GTSAM's ``lago::initialize`` to the letter: a BFS tree instead of
+        the odometric path or a minimum spanning tree, no orientation
+        correction in stage 2, priors used as given instead of an added
+        anchor.  Robust losses are ignored, and a wrong loop closure enters
+        both solves at full weight."""
+        st = L.PgoInitStats()
+        rc = self._L.pgo_initialize_linear(self._h, C.byref(st))
+        self.last_init_stats = st.as_dict()
+        self._check(rc)
+        return self.last_init_stats
+
+    def debug_init_tree(self):
+        """Host-only: initialize_linear's spanning tree -- (parent per vertex,
+        -1 for a root; k per between factor; k per prior), insertion order."""
+        n, np_ = self.num_vertices, self._priors
+        ne = self.num_factors - np_
+        parent = np.zeros(n, np.int32)
+        ke, kp = np.zeros(ne, np.int64), np.zeros(np_, np.int64)
+        llp = C.POINTER(C.c_longlong)
+        self._check(self._L.pgo_debug_init_tree(self._h, parent.ctypes.data_as(C.POINTER(C.c_int)),
+                                                ke.ctypes.data_as(llp), kp.ctypes.data_as(llp), n, ne, np_))
+        return parent, ke, kp
+
+    def debug_init_system(self, stage):
+        """The assembled linear system of initialize_linear's stage 1
+        (orientations) or 2 (positions, at the current orientations) in
+        debug_linearize's layout: (hdiag [n,3,3], hoff [E,3,3], rhs [n,3])."""
+        n = self.num_vertices
+        hd = np.zeros((n, 3, 3))
+        ho = np.zeros((self.num_factors - self._priors, 3, 3))
+        rhs = np.zeros((n, 3))
+        self._check(self._L.pgo_debug_init_system(self._h, int(stage), L.dptr(hd), L.dptr(ho), L.dptr(rhs)))
+        return hd, ho, rhs
+
     def trace(self):
         """Per-iteration record of the last optimize (pgo_get_trace): rows of
         (accepted steps, lambda, solved, model decrease, candidate error,

@@ -337,6 +337,54 @@ int pgo_marginal_covariances(pgo_graph *g, size_t n, const uint64_t *keys, doubl
    A graph with no vertex -> PGO_OK. */
 int pgo_marginal_covariances_all(pgo_graph *g, double *cov, double *edge_cross);
 
+/* ---- linear initialisation (LAGO-style) -----------------------------------
+   Initial values from the graph alone, in two linear solves, so that LM
+   (pgo_optimize) starts inside the basin of convergence instead of at the
+   dead-reckoned values.  The handle's current values are not an input: the
+   result does not depend on them.
+
+   Tree (host).  In every connected component the root is the first vertex, in
+   insertion order, that carries a prior; its tree orientation is the angle of
+   that vertex's first prior.  A FIFO breadth-first search, every vertex
+   scanning its between factors in insertion order whichever end it is, gives
+   each vertex a tree orientation thetaT: parent's + delta_e over a factor
+   (parent, vertex), parent's - delta_e over (vertex, parent), with delta_e =
+   atan2(sin z_theta, cos z_theta); thetaT is not wrapped.  Then per between
+   factor k_e = rint((thetaT[k2] - thetaT[k1] - delta_e) / 2 pi) and per prior
+   k_q = rint((thetaT[v] - theta_q) / 2 pi) fix the 2 pi ambiguities.
+   Stage 1 (device): the orientations minimise
+     sum_e w_e (th_k2 - th_k1 - delta_e - 2 pi k_e)^2 + sum_q w_q (th_v - theta_q - 2 pi k_q)^2,
+   w the information of the angle with the translation marginalised out.
+   Stage 2 (device): the positions minimise the graph's Gaussian error
+   (pgo_error without a loss) with every orientation held at stage 1's: the
+   exact minimiser, one linear solve.
+   Both systems have the sparsity of H and run through the Cholesky solver's
+   plan (one undamped factorisation and solve each).  The result replaces the
+   handle's values; a following pgo_optimize starts from it.
+
+   Not GTSAM's lago::initialize to the letter: the spanning tree is the
+   breadth-first one (GTSAM: the odometric path or a minimum spanning tree),
+   stage 2 applies no orientation correction, and the priors are used as given
+   (GTSAM adds an anchor).  Robust losses are ignored in both stages, as if
+   every factor were PGO_LOSS_NONE, and the initialiser is not robust itself:
+   a wrong loop closure enters both solves at full weight.
+
+   A component without a prior -> PGO_E_INDETERMINANT before any device work; a
+   non-positive pivot in either solve -> PGO_E_INDETERMINANT; a factorisation
+   whose in-launch hand-off timed out -> PGO_E_HIP (it is never re-run inside
+   the call, so a success has no hidden retry); the values are then as they
+   were on entry.  A factor on a key never inserted ->
+   PGO_E_NO_KEY.  No vertex -> PGO_OK.  With a communicator of more than one
+   rank every rank runs the call on its own one-rank plan and gets the same
+   bits.  pgo_optimize never calls it. */
+typedef struct {
+  int status, components, tree_depth;  /* tree_depth: edges on the longest root-to-vertex tree path */
+  long long wraps;                     /* sum |k_e| */
+  double error_before, error_after;    /* pgo_error before / after */
+  double ms_total, ms_tree, ms_orient, ms_trans;  /* wall; host BFS; each stage's assembly+factor+solve */
+} pgo_init_stats;
+int pgo_initialize_linear(pgo_graph *g, pgo_init_stats *stats);   /* stats may be NULL */
+
 /* ---- loop-closure candidate search -----------------------
    The closest_keyframe service (graph.cpp:146-178): among the vertices in
    insertion order except the last `skip` (keyframes_to_skip_in_loop_closing,
@@ -486,6 +534,19 @@ int pgo_debug_plan(pgo_graph *g, double *out, int cap);
  * buffer; 0 would be an in-place pass), out[3] levels; from out[4] the
  * launches of each level, leaves first. */
 int pgo_debug_selinv_plan(pgo_graph *g, double *out, int cap);
+/* Host-only, no device: pgo_initialize_linear's spanning tree.  parent: the
+ * tree parent of every vertex (insertion index, -1 for a root); k_edge: k_e per
+ * between factor, insertion order; k_prior: k_q per prior, insertion order.
+ * Arrays are filled up to their caps.  Returns the vertex count, or
+ * PGO_E_INDETERMINANT (a component without a prior) / PGO_E_NO_KEY. */
+int pgo_debug_init_tree(pgo_graph *g, int *parent, long long *k_edge, long long *k_prior, size_t cap_v,
+                        size_t cap_e, size_t cap_p);
+/* Device: the assembled linear system of stage 1 or 2 of pgo_initialize_linear
+ * in pgo_debug_linearize's layout: hdiag 9 per vertex, hoff the block (k1, k2)
+ * of every between factor, 9 each, insertion order, rhs 3 per vertex.  Stage 1
+ * fills the theta slot (the (x, y) slots an identity), stage 2 the (x, y) slots;
+ * stage 2 is assembled at the handle's current orientations.  The values stay. */
+int pgo_debug_init_system(pgo_graph *g, int stage, double *hdiag, double *hoff, double *rhs);
 /* Host-only, no handle: the optimiser's control (the lambda sequence, the
  * accept / stop rules, the lane rule, the counters) driven as pgo_optimize
  * drives it over `ranks` x `lanes` tries per round, on recorded tries instead

@@ -152,6 +152,23 @@ class NonlinearFactorGraph {  // gtsam::NonlinearFactorGraph
   std::vector<BetweenFactor<Pose2>> betweens_;
 };
 
+// The values' poses, then the graph's priors and between factors, into a handle
+// (insertion order; a robust model travels as the factor's loss and k).
+inline void load_graph(pgo_graph* g, const NonlinearFactorGraph& graph, const Values& values) {
+  for (size_t i = 0; i < values.size(); i++) {
+    const Pose2& p = values.poses()[i];
+    throw_status(pgo_add_vertex(g, values.keys()[i], p.x(), p.y(), p.raw_theta()), g);
+  }
+  for (const auto& f : graph.priors()) {
+    const double z[3] = {f.prior.x(), f.prior.y(), f.prior.raw_theta()};
+    throw_status(pgo_add_prior(g, f.key, z, f.noise.cov.m), g);
+  }
+  for (const auto& f : graph.betweens()) {
+    const double z[3] = {f.measured.x(), f.measured.y(), f.measured.raw_theta()};
+    throw_status(pgo_add_edge_robust(g, f.key1, f.key2, z, f.noise.cov.m, f.loss, f.k), g);
+  }
+}
+
 struct LevenbergMarquardtParams {
   pgo_params p;
   LevenbergMarquardtParams() { pgo_default_params(&p); }
@@ -191,18 +208,7 @@ class LevenbergMarquardtOptimizer {
 
  private:
   void load() {
-    for (size_t i = 0; i < initial_.size(); i++) {
-      const Pose2& p = initial_.poses()[i];
-      throw_status(pgo_add_vertex(g_, initial_.keys()[i], p.x(), p.y(), p.raw_theta()), g_);
-    }
-    for (const auto& f : graph_.priors()) {
-      const double z[3] = {f.prior.x(), f.prior.y(), f.prior.raw_theta()};
-      throw_status(pgo_add_prior(g_, f.key, z, f.noise.cov.m), g_);
-    }
-    for (const auto& f : graph_.betweens()) {
-      const double z[3] = {f.measured.x(), f.measured.y(), f.measured.raw_theta()};
-      throw_status(pgo_add_edge_robust(g_, f.key1, f.key2, z, f.noise.cov.m, f.loss, f.k), g_);
-    }
+    load_graph(g_, graph_, initial_);
     loaded_ = true;
   }
 
@@ -213,6 +219,36 @@ class LevenbergMarquardtOptimizer {
   pgo_stats stats_{};
   bool loaded_ = false;
 };
+
+// gtsam::lago::initialize(graph, values): linear initial values for LM, two
+// linear solves on the device (pgo_initialize_linear): the orientations, then
+// the positions with the orientations held.  `values` only names the keys, as
+// in GTSAM's two-argument form; its poses are not used.  Deviations from
+// GTSAM's lago: the spanning tree is breadth-first from each component's first
+// vertex with a prior (GTSAM: the odometric path, or a minimum spanning tree);
+// stage 2 applies no orientation correction; the graph's priors are used as
+// given (GTSAM adds an anchor), so a component without one throws
+// IndeterminantLinearSystemException.  Robust noise models count as their
+// Gaussian part.
+namespace lago {
+inline Values initialize(const NonlinearFactorGraph& graph, const Values& values, int device = 0) {
+  pgo_opts o{};
+  o.device = device;
+  struct Handle {
+    pgo_graph* g;
+    ~Handle() { pgo_destroy(g); }
+  } h{pgo_create(&o)};
+  if (!h.g) throw std::runtime_error("pgo_create failed");
+  load_graph(h.g, graph, values);
+  throw_status(pgo_initialize_linear(h.g, nullptr), h.g);
+  std::vector<double> xyt(3 * values.size());
+  throw_status(pgo_get_poses(h.g, values.size(), nullptr, xyt.data()), h.g);
+  Values out;
+  for (size_t i = 0; i < values.size(); i++)
+    out.insert(values.keys()[i], Pose2(xyt[3 * i], xyt[3 * i + 1], xyt[3 * i + 2]));
+  return out;
+}
+}  // namespace lago
 
 // gtsam::Marginals(graph, values) (graph.cpp:120, commented in the reference):
 // marginalCovariance(key) is the pose's 3x3 covariance (x, y, theta) at `values`,
@@ -225,18 +261,7 @@ class Marginals {
     g_ = pgo_create(&o);
     if (!g_) throw std::runtime_error("pgo_create failed");
     n_ = values.size();
-    for (size_t i = 0; i < values.size(); i++) {
-      const Pose2& p = values.poses()[i];
-      throw_status(pgo_add_vertex(g_, values.keys()[i], p.x(), p.y(), p.raw_theta()), g_);
-    }
-    for (const auto& f : graph.priors()) {
-      const double z[3] = {f.prior.x(), f.prior.y(), f.prior.raw_theta()};
-      throw_status(pgo_add_prior(g_, f.key, z, f.noise.cov.m), g_);
-    }
-    for (const auto& f : graph.betweens()) {
-      const double z[3] = {f.measured.x(), f.measured.y(), f.measured.raw_theta()};
-      throw_status(pgo_add_edge_robust(g_, f.key1, f.key2, z, f.noise.cov.m, f.loss, f.k), g_);
-    }
+    load_graph(g_, graph, values);
   }
   ~Marginals() { pgo_destroy(g_); }
   Marginals(const Marginals&) = delete;
