@@ -174,6 +174,7 @@ def lib():
         "pgo_debug_factor_time": (C.c_int, [vp, C.c_int, C.c_int, dp]),
         "pgo_debug_poison_fronts": (C.c_int, [vp]),
         "pgo_debug_plan": (C.c_int, [vp, dp, C.c_int]),
+        "pgo_debug_plan_digest": (C.c_int, [vp, C.c_int, C.c_int, u64p, C.c_int]),
         "pgo_marginal_covariances": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_uint64), dp]),
         "pgo_marginal_covariances_all": (C.c_int, [vp, dp, dp]),
         "pgo_debug_selinv_plan": (C.c_int, [vp, dp, C.c_int]),

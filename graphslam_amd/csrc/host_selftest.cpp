@@ -15,10 +15,12 @@
 #include <map>
 #include <tuple>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "pgo_chol.h"
 #include "pgo_lm.h"
+#include "pgo_plan_digest.h"
 #include "pgo_structure.h"
 
 namespace {
@@ -66,6 +68,53 @@ Pattern make_pattern(int n, int lc, unsigned seed, const std::vector<std::pair<i
     P.row_ptr.push_back((int)P.col.size());
   }
   return P;
+}
+
+// block pattern of H for n poses tied pairwise by `e`
+Pattern pattern_of(int n, const std::vector<std::pair<int, int>>& e) {
+  std::vector<std::vector<int>> adj(n);
+  for (const auto& [a, b] : e) adj[a].push_back(b), adj[b].push_back(a);
+  Pattern G;
+  G.n = n;
+  G.row_ptr.assign(1, 0);
+  for (int i = 0; i < n; i++) {
+    adj[i].push_back(i);
+    std::sort(adj[i].begin(), adj[i].end());
+    adj[i].erase(std::unique(adj[i].begin(), adj[i].end()), adj[i].end());
+    G.col.insert(G.col.end(), adj[i].begin(), adj[i].end());
+    G.row_ptr.push_back((int)G.col.size());
+  }
+  return G;
+}
+
+// a side x side grid of poses, each tied to its right and lower neighbour
+Pattern make_grid(int side) {
+  std::vector<std::pair<int, int>> e;
+  for (int y = 0; y < side; y++)
+    for (int x = 0; x < side; x++) {
+      if (x + 1 < side) e.emplace_back(y * side + x, y * side + x + 1);
+      if (y + 1 < side) e.emplace_back(y * side + x, (y + 1) * side + x);
+    }
+  return pattern_of(side * side, e);
+}
+
+// `leaves` cliques of 3 poses, each tied to every pose of a middle clique of 25
+// and of a top clique of 30; a second middle clique of 25 tied to the top alone
+// (it keeps the first from merging into the top); numbered in that order.
+// Eliminated as numbered, the first middle front gets a rectangle from every
+// leaf it has not absorbed in the tiles of its update matrix.
+Pattern make_fan(int leaves) {
+  const int m0 = 3 * leaves, m1 = m0 + 25, t0 = m1 + 25, n = t0 + 30;
+  auto middle = [&](int a) { return a >= m0 && a < m1; };
+  std::vector<std::pair<int, int>> e;
+  for (int a = m0; a < n; a++)
+    for (int b = a + 1; b < n; b++)
+      if (!middle(a) || b < m1 || b >= t0) e.emplace_back(a, b);
+  for (int l = 0; l < leaves; l++)
+    for (int a = 3 * l; a < 3 * l + 3; a++)
+      for (int b = a + 1; b < n; b++)
+        if (b < 3 * l + 3 || middle(b) || b >= t0) e.emplace_back(a, b);
+  return pattern_of(n, e);
 }
 
 // the pattern restricted to poses [0, n)
@@ -403,7 +452,7 @@ int check_splice(const pgo::CholPlan& P, const pgo::GraphStructure& S) {
 // consistent, every front's below rows sit in its parent at the extend-add
 // map's index, the sizes match the row lists, and the structure holds the exact
 // fill of the plan's own ordering (a fresh analysis on P.perm) and the whole pattern.
-int check_append(const TestGraph& G, int n_all, int n0, int ordering) {
+int check_append(const TestGraph& G, int n_all, int n0, int ordering, pgo::CholPlan* keep = nullptr) {
   auto upto = [&](int lo, int hi) {   // the factors whose later pose is in [lo, hi)
     TestGraph g;
     for (const int2& f : G.e)
@@ -475,7 +524,8 @@ int check_append(const TestGraph& G, int n_all, int n0, int ordering) {
     if (S.codes() != F.codes() || S.eside() != F.eside() || S.row_ptr != F.row_ptr || S.slot_col != F.slot_col)
       return fail("append: the structure differs from a rebuild");
   }
-  std::printf("append: %d poses onto %d, %d fronts, flops %.3g\n", n_all - n0, n0, P.ns, P.flops);
+  if (keep) *keep = P;
+  else std::printf("append: %d poses onto %d, %d fronts, flops %.3g\n", n_all - n0, n0, P.ns, P.flops);
   return 0;
 }
 
@@ -1078,9 +1128,66 @@ int check_lm() {
   return 0;
 }
 
+// --digest: one line per built-in case -- the case, the plan's section digests
+// (pgo_plan_digest.h), the branch counters.  The planner's knobs come from the
+// environment (scripts/plan_digests.py runs the set, a fresh process each).
+void digest_line(const std::string& name, const pgo::CholPlan& P) {
+  uint64_t d[pgo::kDigestSections];
+  long long br[pgo::kBranchCounters];
+  pgo::plan_digest(P, d);
+  pgo::plan_branch_counters(P, br);
+  std::printf("%s", name.c_str());
+  for (uint64_t v : d) std::printf(" %016llx", (unsigned long long)v);
+  std::printf(" |");
+  for (long long v : br) std::printf(" %lld", v);
+  std::printf("\n");
+}
+
+int digest_cases() {
+  std::printf("# case");
+  for (const char* s : pgo::kDigestSectionNames) std::printf(" %s", s);
+  std::printf(" |");
+  for (const char* s : pgo::kBranchCounterNames) std::printf(" %s", s);
+  std::printf("\n");
+  const std::pair<const char*, Pattern> graphs[] = {{"tiny5", restrict_pattern(make_pattern(40, 0, 3), 5)},
+                                                    {"chain3000", make_pattern(3000, 400, 7)},
+                                                    {"grid60", make_grid(60)},
+                                                    {"grid100", make_grid(100)}};
+  for (const auto& [gname, G] : graphs)
+    for (int ordering : {pgo::kOrderNd, pgo::kOrderAmd})
+      for (int size : {1, 2, 4, 8})
+        for (int r = 0; r < size; r++) {
+          pgo::CholPlan P;
+          P.ordering = ordering;
+          P.part_size = size;
+          P.part_rank = r;
+          pgo::chol_analyze(P, G.n, G.row_ptr, G.col);
+          if (P.schedule_error) return fail("digest: panel schedule bookkeeping");
+          digest_line(std::string(gname) + (ordering == pgo::kOrderNd ? "/nd/" : "/amd/") + std::to_string(size) + "r" +
+                          std::to_string(r),
+                      P);
+        }
+  {   // a given ordering: the fan's poses as numbered
+    const Pattern G = make_fan(40);
+    pgo::CholPlan P;
+    P.order_in.resize(G.n);
+    for (int k = 0; k < G.n; k++) P.order_in[k] = k;
+    pgo::chol_analyze(P, G.n, G.row_ptr, G.col);
+    if (P.schedule_error || check_first_writes(P)) return fail("digest: fan");
+    digest_line("fan40/given/1r0", P);
+  }
+  for (int ordering : {pgo::kOrderNd, pgo::kOrderAmd}) {
+    pgo::CholPlan P;
+    if (check_append(make_edges(1500, 200, 9, 40), 1500, 1490, ordering, &P)) return 1;
+    digest_line(std::string("append1490+10/") + (ordering == pgo::kOrderNd ? "nd" : "amd"), P);
+  }
+  return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "--digest")) return digest_cases();
   if (check_lm()) return 1;
   if (check_structure()) return 1;
   for (int n : {1, 2, 5}) {   // graphs smaller than the planner's thread count
@@ -1137,27 +1244,7 @@ int main() {
   {   // a 2-D grid of poses: nested dissection gives big separator fronts (many
       // panels, kKB block boundaries, partial last panels) -- the look-ahead
       // schedule's bookkeeping is checked on them
-    const int side = 60, n = side * side;
-    std::vector<std::pair<int, int>> e;
-    for (int y = 0; y < side; y++)
-      for (int x = 0; x < side; x++) {
-        if (x + 1 < side) e.emplace_back(y * side + x, y * side + x + 1);
-        if (y + 1 < side) e.emplace_back(y * side + x, (y + 1) * side + x);
-      }
-    std::vector<std::vector<int>> adj(n);
-    for (auto& [a, b] : e) {
-      adj[a].push_back(b);
-      adj[b].push_back(a);
-    }
-    Pattern G;
-    G.n = n;
-    G.row_ptr.assign(1, 0);
-    for (int i = 0; i < n; i++) {
-      adj[i].push_back(i);
-      std::sort(adj[i].begin(), adj[i].end());
-      G.col.insert(G.col.end(), adj[i].begin(), adj[i].end());
-      G.row_ptr.push_back((int)G.col.size());
-    }
+    const Pattern G = make_grid(60);
     pgo::CholPlan P;
     pgo::chol_analyze(P, G.n, G.row_ptr, G.col);
     if (check_tiles(P) || check_first_writes(P)) return 1;

@@ -23,6 +23,7 @@
 
 #include "pgo.h"
 #include "pgo_chol.h"
+#include "pgo_plan_digest.h"
 #include "pgo_comm.h"
 #include "pgo_search.h"
 #include "pgo_device.h"
@@ -2376,6 +2377,22 @@ int pgo_debug_plan(pgo_graph* g, double* out, int cap) {
     out[o++] = (double)tiles;
   }
   return PGO_OK;
+}
+
+int pgo_debug_plan_digest(pgo_graph* g, int part_size, int part_rank, uint64_t* out, int cap) {
+  if (!g || part_size < 1 || part_rank < 0 || part_rank >= part_size || cap < 0 || (cap > 0 && !out)) return PGO_E_ARG;
+  pgo::GraphStructure H;
+  pgo::CholPlan P;
+  P.part_size = part_size;
+  P.part_rank = part_rank;
+  RC_TRY(analyze_host_graph(g, H, P));
+  uint64_t v[pgo::kDigestSections + pgo::kBranchCounters];
+  long long br[pgo::kBranchCounters];
+  pgo::plan_digest(P, v);
+  pgo::plan_branch_counters(P, br);
+  for (int i = 0; i < pgo::kBranchCounters; i++) v[pgo::kDigestSections + i] = (uint64_t)br[i];
+  for (int i = 0; i < cap && i < pgo::kDigestSections + pgo::kBranchCounters; i++) out[i] = v[i];
+  return pgo::kDigestSections;
 }
 
 int pgo_debug_selinv_plan(pgo_graph* g, double* out, int cap) {

@@ -355,12 +355,35 @@ std::vector<int> partition_subtrees(const CholPlan& P, int size, std::vector<dou
 // returned in *replicated)
 std::vector<double> distributed_rank_flops(const CholPlan& P, int size, double* replicated = nullptr);
 
+// host: column owners of the distributed top (chol_schedule): per top front s
+// (owner[s] < 0) its m columns at cown[off[s] ..]: rank, or -1 (every rank)
+void column_owners(const CholPlan& P, const std::vector<int>& owner, int psz, std::vector<int>& off,
+                   std::vector<int>& cown);
+
+// host: sum_{t=1..x} min(t, c): the elements of a child rectangle inside the
+// child's lower triangle are a difference of two (level_at_bytes, fuse_level)
+inline long long ramp_sum(long long x, long long c) {
+  if (x <= 0) return 0;
+  return x <= c ? x * (x + 1) / 2 : c * (c + 1) / 2 + (x - c) * c;
+}
+
+// host: v.resize(n) leaving room when it has to grow (the live path's plan
+// refreshes then resize within capacity: no reallocation and copy of the whole list)
+template <class V>
+void resize_room(V& v, size_t n) {
+  if (v.capacity() < n) v.reserve(n + n / 16 + 1024);
+  v.resize(n);
+}
+
 // host: fn(t) for t in [0, ntask) on the planner's thread pool (the caller
 // takes part; PGO_PLAN_THREADS threads, default the hardware's, at most 16)
 void plan_parallel(int ntask, const std::function<void(int)>& fn);
 
 // host: symbolic analysis from the block-CSR pattern (old pose indices)
 void chol_analyze(CholPlan& P, int n, const std::vector<int>& row_ptr, const std::vector<int>& slot_col);
+// host: the plan's schedules from its fronts -- chol_analyze's second half, re-run
+// by chol_append on the updated fronts (pgo_schedule.cpp)
+void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& slot_col);
 // host: (re)build the plan's H assembly lists for a pattern its fronts hold
 void chol_assembly(CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& slot_col);
 double level_at_bytes(const CholPlan& P, int L);

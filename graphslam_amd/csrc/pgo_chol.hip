@@ -1,5 +1,5 @@
 // GPU supernodal multifrontal Cholesky of H + lambda I and its triangular
-// solves (gfx950).  Host plan: pgo_symbolic.cpp; layout: pgo_chol.h.
+// solves (gfx950).  Host plan: pgo_symbolic.cpp, pgo_schedule.cpp; layout: pgo_chol.h.
 //
 // Factorisation, per level of the supernodal tree (leaves first):
 //   k_assemble_tile every front of the level, one workgroup per 64x64 lower
@@ -3273,11 +3273,6 @@ static void launch(LaunchProfile* prof, int fam, Cost cost, K kern, dim3 grid, d
 double level_at_bytes(const CholPlan& P, int L) {
   const CholLevel& lv = P.levels[L];
   if (lv.at_bytes >= 0) return lv.at_bytes;
-  // sum_{t=A..B} clamp(t, 0, c) in closed form (G(x) = sum_{t=1..x} min(t, c))
-  auto G = [](long long x, long long c) -> long long {
-    if (x <= 0) return 0;
-    return x <= c ? x * (x + 1) / 2 : c * (c + 1) / 2 + (x - c) * c;
-  };
   double bytes = 0;
   for (int q = lv.ea_off[0]; q < lv.ea_off[0] + lv.ea_cnt[0]; q++) {
     const int4 t = P.ea_tasks[q];
@@ -3285,7 +3280,7 @@ double level_at_bytes(const CholPlan& P, int L) {
     for (int k = 0; k < t.w; k++) {   // rows r < nr of a child rectangle: min(max(a0 + r - b0 + 1, 0), nc) columns
       const int4 pr = P.ea_pairs[t.z + k];
       const long long nr = pr.w & 0xff, ncl = pr.w >> 8, d = pr.y - pr.z + 1;
-      e += (double)(G(d + nr - 1, ncl) - G(d - 1, ncl));
+      e += (double)(ramp_sum(d + nr - 1, ncl) - ramp_sum(d - 1, ncl));   // sum_{t=A..B} clamp(t, 0, c)
     }
     const int2 it = P.at_iptr[q];
     for (int k = 0; k < it.y; k++) {

@@ -5,17 +5,13 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
-#include <chrono>
 #include <thread>
-#include <tuple>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "pgo_chol.h"
+#include "pgo_structure.h"
 
 namespace pgo {
 
@@ -117,105 +113,9 @@ std::vector<int> order_amd(int n, const std::vector<int>& xadj, const std::vecto
   return order;
 }
 
-void xcd_order(std::vector<int4>& tasks, int tile) {
-  constexpr int kXcd = 8, kBlk = 8;
-  if ((int)tasks.size() < 4 * kXcd * kBlk) return;   // small launches: keep the natural order
-  const int span = tile * kBlk;
-  // (front, column block, row block) packed in the high bits, the task index in
-  // the low 32: a plain sort of the keys is the stable sort by block
-  // (block indices below 2^16: rows and columns below 2^20, span >= 512)
-  using u128 = unsigned __int128;
-  std::vector<u128> key(tasks.size());
-  for (size_t i = 0; i < tasks.size(); i++) {
-    const int4& t = tasks[i];
-    const unsigned long long blk = (unsigned long long)(unsigned)t.x << 32 | (unsigned long long)(t.z / span) << 16 |
-                                   (unsigned)((t.y & kRowMask) / span);
-    key[i] = (u128)blk << 32 | i;
-  }
-  std::sort(key.begin(), key.end());
-  std::vector<std::vector<int4>> q(kXcd);
-  for (auto& v : q) v.reserve(tasks.size() / kXcd + 1);
-  int blk = -1;
-  unsigned long long prev = ~0ull;
-  for (const u128 k : key) {
-    if ((unsigned long long)(k >> 32) != prev) {
-      blk++;
-      prev = (unsigned long long)(k >> 32);
-    }
-    q[blk % kXcd].push_back(tasks[(size_t)(k & 0xffffffffu)]);
-  }
-  std::vector<int4> out;
-  out.reserve(tasks.size());
-  std::vector<size_t> pos(kXcd, 0);
-  for (size_t left = tasks.size(); left;)
-    for (int x = 0; x < kXcd; x++)
-      if (pos[x] < q[x].size()) {
-        out.push_back(q[x][pos[x]++]);
-        left--;
-      }
-  tasks.swap(out);
-}
-
-// XCD-aware order of a level's tile-assembly tasks [off, end): a child's
-// update-matrix column lands on a parent column as one run of child rows that
-// crosses the parent's row tiles, so vertically adjacent tiles read the same
-// 128-byte lines at their run boundaries.  Blocks of kCols x kRows tiles of a
-// front, column-major inside, are dealt round-robin to the 8 XCDs (blockIdx
-// b -> XCD b % 8 as observed: speed only, each tile is computed alike
-// wherever and whenever it runs).  PGO_ASM_XCD=0 keeps the natural order;
-// 2 orders every level, however few its tiles (host self-test).
-static void ea_xcd_order(std::vector<int4>& tasks, size_t off) {
-  constexpr int kXcd = 8, kCols = 4, kRows = 16;
-  static const int mode = getenv("PGO_ASM_XCD") ? atoi(getenv("PGO_ASM_XCD")) : 1;
-  const size_t n = tasks.size() - off;
-  if (mode == 0 || (mode == 1 && n < (size_t)4 * kXcd * kCols * kRows)) return;
-  // key: (block of the front in order of first appearance, column, row), task index
-  using u128 = unsigned __int128;
-  std::vector<u128> key(n);
-  int blk = -1, fprev = -1;
-  std::vector<int> bid;   // the front's blocks: (tj / kCols, ti / kRows) -> block number
-  int nbr = 0;
-  for (size_t i = 0; i < n; i++) {
-    const int4& t = tasks[off + i];
-    const int ti = t.y >> 16, tj = t.y & 0xffff;
-    if (t.x != fprev) {   // a front's tasks are contiguous (row-major lower triangle)
-      fprev = t.x;
-      int nt = 0;
-      for (size_t k = i; k < n && tasks[off + k].x == t.x; k++) nt = std::max(nt, (tasks[off + k].y >> 16) + 1);
-      nbr = (nt + kRows - 1) / kRows;
-      bid.assign((size_t)((nt + kCols - 1) / kCols) * nbr, -1);
-    }
-    int& b = bid[(size_t)(tj / kCols) * nbr + ti / kRows];
-    if (b < 0) b = ++blk;
-    key[i] = (u128)((unsigned long long)b << 32 | (unsigned)tj << 16 | (unsigned)ti) << 32 | i;
-  }
-  std::sort(key.begin(), key.end());
-  std::vector<std::vector<int4>> q(kXcd);
-  for (const u128 k : key) q[(int)(k >> 64) % kXcd].push_back(tasks[off + (size_t)(k & 0xffffffffu)]);
-  std::vector<size_t> pos(kXcd, 0);
-  size_t o = off;
-  for (size_t left = n; left;)
-    for (int x = 0; x < kXcd; x++)
-      if (pos[x] < q[x].size()) {
-        tasks[o++] = q[x][pos[x]++];
-        left--;
-      }
-}
-
-// dense Cholesky flops of the w pivot columns of an m-row front, plus the
-// inverses of its diagonal blocks (what the small-front kernels form)
-static double front_flops(int m, int w) {
-  double f = (double)w * w * w / 3.0;
-  for (int k = 0; k < w; k++) {
-    const double r = m - k - 1;
-    f += 1 + r + r * (r + 1);
-  }
-  return f;
-}
-
 // Column owners of the distributed top (see chol_analyze): per top front s
 // (owner[s] < 0) its m columns at cown[off[s] ..]: rank, or -1 (every rank).
-static void column_owners(const CholPlan& P, const std::vector<int>& owner, int psz, std::vector<int>& off,
+void column_owners(const CholPlan& P, const std::vector<int>& owner, int psz, std::vector<int>& off,
                           std::vector<int>& cown) {
   const int ns = P.ns;
   off.assign(ns, -1);
@@ -367,118 +267,12 @@ PlanPool& plan_pool() {
 
 void plan_parallel(int ntask, const std::function<void(int)>& fn) { plan_pool().run(ntask, fn); }
 
-// v.resize(n) leaving room when it has to grow (the live path's plan refreshes
-// then resize within capacity: no reallocation and copy of the whole list)
-template <class V>
-static void resize_room(V& v, size_t n) {
-  if (v.capacity() < n) v.reserve(n + n / 16 + 1024);
-  v.resize(n);
-}
-
 // fn(t, begin, end) on nth contiguous chunks of [0, n), chunk t by index (the
 // results are independent of which thread runs it and of nth)
 template <class F>
 static void parallel_chunks(int n, int nth, F&& fn) {
   nth = std::max(1, std::min(nth, n));
   plan_parallel(nth, [&](int t) { fn(t, (int)((long long)n * t / nth), (int)((long long)n * (t + 1) / nth)); });
-}
-
-// One level's share of the schedule lists (chol_schedule builds the levels
-// concurrently, then appends them to the plan's lists in level order).
-struct LevelLists {
-  std::vector<int> small_list, level_fronts, potrf_list;
-  std::vector<int4> syrk_tasks, sdiag_tasks, col_tasks, bwd_tasks, bwdc_tasks, bwd_part_tasks, ea_tasks, ea_pairs;
-  std::vector<int2> bwd_pref;
-  std::vector<int2> syrk_gather;   // per syrk task (fuse_level)
-  long long fused = 0, fused_with_pairs = 0, fused_multipass = 0, fused_edge = 0;
-  std::vector<XExchange> xchg;
-  std::vector<int4> xp_tasks;
-  std::vector<long long> xp_loff, xp_lstride;
-  long long xp_rslot = 0;
-  int npart = 0;
-  bool schedule_error = false;
-  // empty again, capacity kept
-  void reset() {
-    syrk_gather.clear();
-    fused = fused_with_pairs = fused_multipass = fused_edge = 0;
-    for (auto* v : {&small_list, &level_fronts, &potrf_list}) v->clear();
-    for (auto* v : {&syrk_tasks, &sdiag_tasks, &col_tasks, &bwd_tasks, &bwdc_tasks, &bwd_part_tasks, &ea_tasks, &ea_pairs,
-                    &xp_tasks})
-      v->clear();
-    bwd_pref.clear();
-    xchg.clear();
-    xp_loff.clear();
-    xp_lstride.clear();
-    xp_rslot = 0;
-    npart = 0;
-    schedule_error = false;
-  }
-};
-
-// The plan's schedules from its fronts (chol_analyze's second half; the
-// incremental append re-runs it on the updated fronts): the subtree partition,
-// the level schedules and task lists, then the H assembly lists.
-// The selected-inversion pass's launch lists (pgo_chol.h SelPlan) from the
-// level lists: rebuilt with every schedule, so a re-plan and an incremental
-// append carry them too.  A partitioned plan has none (the pass walks every
-// front: pgo_marginal_covariances_all plans for one rank).
-static void selinv_schedule(CholPlan& P) {
-  SelPlan& Q = P.sel;
-  Q.levels.clear();
-  Q.gather.clear();
-  Q.tiles.clear();
-  Q.diag.clear();
-  Q.goff.assign(P.ns, 0);
-  Q.gmax = Q.pmax = 0;
-  Q.launches = 0;
-  static std::atomic<unsigned> serial{0};   // (unique over plans: a handle's edge table is keyed by it)
-  Q.serial = ++serial;
-  if (P.part_size > 1) return;
-  Q.levels.resize(P.levels.size());
-  Q.launches = 1;   // the read-out
-  std::vector<int> big;   // the level's blocked fronts, in level order
-  for (size_t L = 0; L < P.levels.size(); L++) {
-    const CholLevel& lv = P.levels[L];
-    SelLevel& sl = Q.levels[L];
-    const int* fr = P.level_fronts.data() + lv.front_off;
-    // (every front that is not packed is in one of the level's wavefront
-    // classes, and those sit back to back in small_list)
-    sl.small_off = lv.small.empty() ? 0 : lv.small.front().off;
-    for (const SmallClass& sc : lv.small) sl.small_cnt += sc.cnt;
-    sl.gat_off = (int)Q.gather.size();
-    long long g = 0;
-    int maxblk = 0;
-    big.clear();
-    for (int q = 0; q < lv.front_cnt; q++) {
-      const int s = fr[q], m = P.m[s], w = P.w[s];
-      if (!front_packed(m, w)) continue;
-      big.push_back(s);
-      Q.goff[s] = g;
-      g += 64LL * fpad(m);
-      maxblk = std::max(maxblk, (w + 63) / 64);
-      if (m > w)
-        for (int cb = w / 64; 64 * cb < m; cb++) Q.gather.push_back(make_int2(s, cb));
-    }
-    Q.gmax = std::max(Q.gmax, g);
-    sl.gat_cnt = (int)Q.gather.size() - sl.gat_off;
-    Q.launches += (sl.small_cnt > 0) + (sl.gat_cnt > 0);
-    for (int b = maxblk - 1; b >= 0; b--) {
-      SelStep st{b, (int)Q.tiles.size(), 0, (int)Q.diag.size(), 0};
-      int slot = 0;
-      for (int s : big) {
-        const int m = P.m[s], w = P.w[s], c0 = 64 * b;
-        if (c0 >= w) continue;
-        const int rs = c0 + std::min(64, w - c0), p0 = slot;
-        for (int r0 = rs; r0 < m; r0 += 64) Q.tiles.push_back(make_int4(s, r0, c0, slot++));
-        Q.diag.push_back(make_int4(s, c0, p0, slot - p0));
-      }
-      st.tile_cnt = (int)Q.tiles.size() - st.tile_off;
-      st.diag_cnt = (int)Q.diag.size() - st.diag_off;
-      Q.pmax = std::max<long long>(Q.pmax, slot);
-      Q.launches += 2 * (st.tile_cnt > 0) + 1;
-      sl.steps.push_back(st);
-    }
-  }
 }
 
 double selinv_flops(const CholPlan& P) {
@@ -508,904 +302,8 @@ void selinv_edge_table(const CholPlan& P, const int2* pairs, long long ne, int4*
   });
 }
 
-static void chol_schedule(CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& slot_col) {
-  static const bool timing = getenv("PGO_PLAN_TIMING") != nullptr;
-  auto tlast = std::chrono::steady_clock::now();
-  auto phase = [&](const char* what) {
-    if (!timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "chol_schedule %-12s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tlast).count());
-    tlast = t;
-  };
-  const int ns = P.ns;
-  P.schedule_error = false;
-  // ---- multi-GPU subtree partition (part_size > 1, DESIGN.md "Multi-GPU"):
-  // rank part_rank factorises the fronts of its subtrees (phase 1), then every
-  // rank the replicated top fronts (phase 2), after the subtree roots' update
-  // matrices / vectors have been exchanged.  Storage only for the fronts this
-  // rank touches: its own, the top, and the other ranks' subtree roots (their
-  // update matrices arrive in the exchange).  One rank: everything is phase 1.
-  const int psz = std::max(P.part_size, 1), prk = P.part_rank;
-  P.owner = partition_subtrees(P, psz);
-  P.subtree_cnt.assign(ns, 1);
-  for (int s = 0; s < ns; s++)
-    if (P.parent[s] >= 0) P.subtree_cnt[P.parent[s]] += P.subtree_cnt[s];
-  std::vector<char> need(ns, 0);
-  P.xroot.clear();
-  P.xroot_rank.clear();
-  for (int s = 0; s < ns; s++) {
-    const bool root = P.owner[s] >= 0 && (P.parent[s] < 0 || P.owner[P.parent[s]] < 0);
-    if (root) {
-      P.xroot.push_back(s);
-      P.xroot_rank.push_back(P.owner[s]);
-    }
-    need[s] = P.owner[s] == prk || P.owner[s] < 0 || (root && P.parent[s] >= 0);
-  }
-  if (psz > 1) {   // offsets over the needed fronts only
-    for (int s = 0; s < ns; s++) {
-      P.foff[s + 1] = P.foff[s] + (need[s] ? ((front_elems(P.m[s], P.w[s]) + 15) / 16) * 16 : 0);
-      P.voff[s + 1] = P.voff[s] + (need[s] ? ((P.m[s] + 7) / 8) * 8 : 0);
-      P.toff[s + 1] = P.toff[s] + (need[s] ? (long long)((P.w[s] + 63) / 64) * 4096 : 0);
-    }
-    P.ftotal = P.foff[ns];
-    P.ttotal = P.toff[ns];
-    P.vtotal = P.voff[ns];
-  }
-  // exchange layout: per rank its roots' payloads (packed lower update matrix,
-  // then the update vector) back to back; the solve's: its subtrees' poses
-  P.xroot_off.assign(P.xroot.size(), 0);
-  P.xsize.assign(psz, 0);
-  P.xsol_size.assign(psz, 0);
-  P.xsol_ranges.clear();
-  for (size_t q = 0; q < P.xroot.size(); q++) {
-    const int sr = P.xroot[q], r = P.xroot_rank[q];
-    const long long u = P.m[sr] - P.w[sr];
-    P.xroot_off[q] = P.xsize[r];
-    P.xsize[r] += u * (u + 1) / 2 + u;
-    const int first = sr - P.subtree_cnt[sr] + 1;   // the subtree: postorder fronts [first, sr]
-    P.xsol_ranges.push_back(make_int4(r, 3 * P.sfirst[first], 3 * P.sfirst[sr + 1], (int)P.xsol_size[r]));
-    P.xsol_size[r] += 3LL * (P.sfirst[sr + 1] - P.sfirst[first]);
-  }
-  P.xmax = *std::max_element(P.xsize.begin(), P.xsize.end());
-  P.xsol_max = *std::max_element(P.xsol_size.begin(), P.xsol_size.end());
-  phase("partition");
-  // ---- level schedules: phase 1 (this rank's subtree fronts) then phase 2 (top)
-  std::vector<std::vector<int>> bylevel;
-  for (int phase = 0; phase < 2; phase++) {
-    int hmax = -1;
-    for (int s = 0; s < ns; s++)
-      if ((phase == 0 ? P.owner[s] == prk : P.owner[s] < 0)) hmax = std::max(hmax, P.height[s]);
-    const size_t base = bylevel.size();
-    bylevel.resize(base + hmax + 1);
-    for (int s = 0; s < ns; s++)
-      if ((phase == 0 ? P.owner[s] == prk : P.owner[s] < 0)) bylevel[base + P.height[s]].push_back(s);
-    if (phase == 0) P.split = (int)bylevel.size();
-  }
-  {   // drop empty levels (a height with no front of this rank), keeping the split
-    std::vector<std::vector<int>> kept;
-    int split = 0;
-    for (size_t L = 0; L < bylevel.size(); L++)
-      if (!bylevel[L].empty()) {
-        kept.push_back(std::move(bylevel[L]));
-        if ((int)L < P.split) split++;
-      }
-    bylevel.swap(kept);
-    P.split = split;
-  }
-  // blocked path (64-column panels) vs one workgroup / wavefront per front
-  auto blocked = [&](int s) { return front_packed(P.m[s], P.w[s]); };
-  // ---- distributed top (part_size > 1): the top fronts' columns are dealt to
-  // the ranks instead of every rank factoring every top front.  A blocked top
-  // front's pivot columns go by 64-column panel, round robin (continuing over
-  // the fronts); its columns past the last whole panel (the update matrix) take
-  // the rank of the parent column they extend-add into, so a rank's share of a
-  // parent's columns is assembled from its own shares of the children's update
-  // matrices (no exchange of update matrices between top fronts).  Small top
-  // fronts (one workgroup / wavefront each) are computed by every rank (-1),
-  // and so are the update columns of their children.  Each column's updates
-  // are applied by its rank only, with the same tasks (same depths, same
-  // order) as the one-rank plan: bitwise the one-rank factor.  A rank receives
-  // every panel (broadcast by its owner right after it is factored) for its own
-  // columns' updates and the replicated backward solve.
-  // (PGO_DIST_TOP=0: the top fronts replicated on every rank instead -- the
-  // previous scheme, kept as a reference for the host self-test)
-  const bool dtop = psz > 1 && !(getenv("PGO_DIST_TOP") && atoi(getenv("PGO_DIST_TOP")) == 0);
-  P.cown_off.assign(ns, -1);
-  P.cown.clear();
-  if (dtop) column_owners(P, P.owner, psz, P.cown_off, P.cown);
-  P.xchg.clear();
-  P.xp_tasks.clear();
-  P.xp_loff.clear();
-  P.xp_lstride.clear();
-  P.xp_rslot = 0;
-  // an exchange point: every panel / tail in `items` (front, kn, nb | kind << 16,
-  // owner) goes from its owner to every rank (one broadcast per sending rank)
-  auto add_exchange = [&](LevelLists& S, const std::vector<int4>& items) -> int {
-    if (items.empty()) return -1;
-    XExchange x;
-    x.off = (int)S.xp_tasks.size();
-    x.cnt = (int)items.size();
-    x.size.assign(psz, 0);
-    for (const int4& t : items) {
-      const int s = t.x, kn = t.y, nb = t.z & 0xffff, kind = t.z >> 16, m = P.m[s];
-      // kind 0: the L below the diagonal tile (the tile's own L is never stored),
-      // the inverse, the frontal vector; kind 1: the tail columns whole
-      const long long sz = kind == 0 ? (long long)(m - kn - nb) * nb + 4096 + (m - kn) : (long long)(m - kn) * nb;
-      S.xp_tasks.push_back(t);
-      S.xp_loff.push_back(x.size[t.w]);
-      x.size[t.w] += sz;
-    }
-    for (int q = x.off; q < x.off + x.cnt; q++) S.xp_lstride.push_back(x.size[S.xp_tasks[q].w]);
-    for (long long v : x.size) S.xp_rslot = std::max(S.xp_rslot, v);
-    S.xchg.push_back(x);
-    return (int)S.xchg.size() - 1;
-  };
-  const int nl = (int)bylevel.size();
-  P.levels.assign(nl, CholLevel());
-  // one level's schedule into its own lists (offsets level-relative; merged
-  // below in level order, so the plan is the same for any thread count)
-  auto schedule_level = [&](int L, LevelLists& S, int part) {
-    CholLevel& lv = P.levels[L];
-    // distributed top level: this rank generates only the tasks of its columns
-    const bool dist = dtop && L >= P.split;
-    auto mine = [&](int s, int col) {
-      if (!dist) return true;
-      const int o = P.cown[P.cown_off[s] + col];
-      return o < 0 || o == prk;
-    };
-    auto cowner = [&](int s, int col) { return dist ? P.cown[P.cown_off[s] + col] : -1; };
-    // part 0: the front list, the backward-solve and assembly lists (members of
-    // S and lv disjoint from part 1's: the two parts of a level run concurrently)
-    if (part == 0) {
-      lv.front_off = (int)S.level_fronts.size();
-      lv.front_cnt = (int)bylevel[L].size();
-      for (int s : bylevel[L]) {
-        S.level_fronts.push_back(s);
-        lv.maxm = std::max(lv.maxm, P.m[s]);
-        if (P.m[s] <= kSmallFront) lv.small_maxm = std::max(lv.small_maxm, P.m[s]);
-      }
-      // blocked backward solve (64-column blocks of each front's pivot columns);
-      // the forward substitution is carried by the factorisation
-      for (int s : bylevel[L]) lv.maxblk = std::max(lv.maxblk, (P.w[s] + 63) / 64);
-      {                                            // backward init: all columns vs the rows below w
-        // partial products L21[r0:r0+kBwdRows, block]' x_below, one task each,
-        // reduced in fixed order by the init task of the block
-        SolveStep sp{(int)S.bwd_part_tasks.size(), 0};
-        SolveStep st{(int)S.bwd_tasks.size(), 0};
-        for (int s : bylevel[L]) {
-          const int w = P.w[s], m = P.m[s], nblk = (w + 63) / 64;
-          for (int b = 0; b < nblk; b++) {
-            const int p0 = S.npart;
-            for (int r0 = w; r0 < m; r0 += kBwdRows) S.bwd_part_tasks.push_back(make_int4(s, b * 64, r0, S.npart++));
-            S.bwd_tasks.push_back(make_int4(s, b * 64, std::min(b * 64 + 64, w), b == nblk - 1 ? b : -1));
-            S.bwd_pref.push_back(make_int2(p0, S.npart - p0));
-          }
-        }
-        sp.cnt = (int)S.bwd_part_tasks.size() - sp.off;
-        for (int q = sp.off; q < sp.off + sp.cnt; q++) {
-          const int4 t = S.bwd_part_tasks[q];
-          const double ncol = std::min(64, P.w[t.x] - t.y), rows = std::min(kBwdRows, P.m[t.x] - t.z);
-          lv.bwd_part_flops += 2.0 * ncol * rows;
-          // L rows x columns, x gathered per row (+ its pose index per 3 rows), the 64 partial sums out
-          lv.bwd_part_bytes += 8.0 * ncol * rows + rows * (8.0 + 4.0 / 3.0) + 8.0 * 64;
-        }
-        st.cnt = (int)S.bwd_tasks.size() - st.off;
-        for (int q = st.off; q < st.off + st.cnt; q++) {   // init: partials + y in, X_jj' z for the last block, x out
-          const int4 t = S.bwd_tasks[q];
-          const double n2 = t.z - t.y, np = S.bwd_pref[q].y;
-          lv.bwd_init_bytes += 8.0 * n2 * (np + 2.0) + (t.w >= 0 ? 8.0 * n2 * (64.0 + 1.0) + 4.0 * n2 / 3.0 : 0.0);
-        }
-        // frontal vectors: own rows gathered from the permuted rhs, the children's
-        // update vectors with their row maps, the vector written
-        for (int s : bylevel[L]) {
-          lv.vec_bytes += 8.0 * P.m[s] + (8.0 + 4.0 / 3.0) * P.w[s];
-          for (int q = P.cptr[s]; q < P.cptr[s + 1]; q++) lv.vec_bytes += (8.0 + 4.0 / 3.0) * (P.m[P.children[q]] - P.w[P.children[q]]);
-        }
-        lv.bwd_part = sp;
-        lv.bwd.push_back(st);
-      }
-      {   // the same steps as one chained launch (k_bwd_chain): block j of a front
-          // after the blocks above it, tasks ordered by distance from the last
-          // block so that every workgroup waits only on earlier-dispatched ones
-        lv.bwdc.off = (int)S.bwdc_tasks.size();
-        for (int d = 1; d < lv.maxblk; d++)
-          for (int s : bylevel[L]) {
-            const int w = P.w[s], nblk = (w + 63) / 64;
-            if (d >= nblk) continue;
-            const int j = nblk - 1 - d;
-            S.bwdc_tasks.push_back(make_int4(s, j * 64, j * 64 + 64, j));
-            // L[block b, block j] for every block b below j and its x_b, X_jj, z in, x out
-            const double n2 = std::min(64, w - 64 * j);
-            lv.bwd_chain_bytes += 8.0 * (w - 64.0 * (j + 1)) * (n2 + 1.0) + 8.0 * n2 * (64.0 + 3.0) + 4.0 * n2 / 3.0;
-          }
-        lv.bwdc.cnt = (int)S.bwdc_tasks.size() - lv.bwdc.off;
-      }
-      for (int b = lv.maxblk - 1; b >= 1; b--) {   // backward step b: columns left of block b
-        SolveStep st{(int)S.bwd_tasks.size(), 0};
-        for (int s : bylevel[L]) {
-          const int w = P.w[s], nblk = (w + 63) / 64;
-          if (b >= nblk) continue;
-          for (int c = 0; c < b; c++)
-          {
-            S.bwd_tasks.push_back(make_int4(s, c * 64, c * 64 + 64, c == b - 1 ? c : -1));
-            S.bwd_pref.push_back(make_int2(0, 0));
-          }
-        }
-        st.cnt = (int)S.bwd_tasks.size() - st.off;
-        lv.bwd.push_back(st);
-      }
-      // assembly: one task per 64x64 tile of every front's lower triangle (the
-      // fused ones leave the list in fuse_level), which it writes whole: its H entries (+ lambda on the diagonal), then the
-      // update-matrix elements of the front's children in order (fixed
-      // summation order, no atomics), each child contributing a rectangle of its
-      // update matrix (child rows [a0, a0+nr) x columns [b0, b0+nc), the rows /
-      // columns whose parent index falls in the tile).  No front is zeroed.
-      lv.ea_off.push_back((int)S.ea_tasks.size());
-      std::vector<int> tcnt, tpos;
-      std::vector<int4> runs;   // (child, tile, first child row, rows) of every child, children in order
-      for (int sp : bylevel[L]) {
-        const int nt = (P.m[sp] + 63) / 64;
-        tcnt.assign((size_t)nt * (nt + 1) / 2, 0);
-        runs.clear();
-        std::vector<int> cr(1, 0);   // runs of child q: [cr[q], cr[q + 1])
-        for (int q = P.cptr[sp]; q < P.cptr[sp + 1]; q++) {
-          const int c = P.children[q];
-          const int u = P.m[c] - P.w[c];
-          const size_t r0 = runs.size();
-          const int* rel = P.ea_rel.data() + P.ea_ptr[c];
-          auto add = [&](int t, int a, int nr) {
-            if (runs.size() == r0 || runs.back().y != t) runs.push_back(make_int4(c, t, a, 0));
-            runs.back().w += nr;
-          };
-          // (row a of the update matrix: parent row 3 rel[a / 3] + a % 3; a pose's
-          // three rows in one tile go as one)
-          for (int a = 0; a < u; a += 3) {
-            const int r = 3 * rel[a / 3];
-            if ((r >> 6) == ((r + 2) >> 6) && a + 3 <= u) {
-              add(r >> 6, a, 3);
-            } else {
-              for (int k = 0; k < 3 && a + k < u; k++) add((r + k) >> 6, a + k, 1);
-            }
-          }
-          for (size_t i = r0; i < runs.size(); i++)   // a child's runs are in increasing tiles: one pair per tile
-            for (size_t j = r0; j <= i; j++) tcnt[(size_t)runs[i].y * (runs[i].y + 1) / 2 + runs[j].y]++;
-          cr.push_back((int)runs.size());
-        }
-        const int base = (int)S.ea_pairs.size();
-        tpos.assign(tcnt.size(), 0);
-        for (size_t k = 1; k < tcnt.size(); k++) tpos[k] = tpos[k - 1] + tcnt[k - 1];
-        for (int ti = 0; ti < nt; ti++)
-          for (int tj = 0; tj <= ti; tj++) {
-            const size_t k = (size_t)ti * (ti + 1) / 2 + tj;
-            S.ea_tasks.push_back(make_int4(sp, (ti << 16) | tj, base + tpos[k], tcnt[k]));
-          }
-        S.ea_pairs.resize(base + (tcnt.empty() ? 0 : tpos.back() + tcnt.back()));
-        for (size_t q = 0; q + 1 < cr.size(); q++)   // children in order: their pairs in order within every tile
-          for (int i = cr[q]; i < cr[q + 1]; i++)
-            for (int j = cr[q]; j <= i; j++) {
-              const size_t k = (size_t)runs[i].y * (runs[i].y + 1) / 2 + runs[j].y;
-              S.ea_pairs[base + tpos[k]++] = make_int4(runs[i].x, runs[i].z, runs[j].z, runs[i].w | (runs[j].w << 8));
-            }
-      }
-      // (fuse_level takes the fused tiles out, orders the rest and sets ea_cnt)
-      return;
-    }
-    // part 1: the factorisation lists (small-front classes, blocked panel steps)
-    // small fronts (m <= kSmallFront): with w <= kWaveW one wavefront each (the
-    // m x w panel in LDS, the rank-w Schur update streamed), largest first;
-    // else one workgroup each with the whole front in LDS, launched per size
-    // class so the LDS request (m^2 doubles) does not cap the occupancy
-    std::vector<int> big;
-    {
-      const int classes[4] = {32, 64, 96, kSmallFront};
-      std::vector<int> bucket[4], wave;
-      for (int s : bylevel[L]) {
-        // w > kWaveW: the blocked path (64-column panels, every front of the
-        // level in the same launches) -- a whole-front-in-LDS workgroup runs
-        // its w pivots one after the other at ~2 us each
-        if (blocked(s)) {
-          big.push_back(s);
-          continue;
-        }
-        if (P.w[s] <= kWaveW) {
-          wave.push_back(s);
-          continue;
-        }
-        int q = 0;
-        while (P.m[s] > classes[q]) q++;
-        bucket[q].push_back(s);
-      }
-      // m <= 64 (one row per lane) | 64 < m <= 128  x  w <= 8 | 16 | 32
-      for (int cls = 0; cls < 6; cls++) {
-        const int rc = cls / 3, W = cls % 3 == 0 ? 8 : cls % 3 == 1 ? 16 : kWaveW;
-        const int Wlo = cls % 3 == 0 ? 0 : W / 2;
-        std::vector<int> part;
-        for (int s : wave) {
-          const int mc = P.m[s] <= 64 ? 0 : 1;
-          if (mc == rc && P.w[s] > Wlo && P.w[s] <= W) part.push_back(s);
-        }
-        if (part.empty()) continue;
-        std::stable_sort(part.begin(), part.end(), [&](int a, int b) {
-          const double wa = (double)P.m[a] * P.m[a] * P.w[a], wb = (double)P.m[b] * P.m[b] * P.w[b];
-          return wa > wb;
-        });
-        SmallClass sc{(int)S.small_list.size(), (int)part.size(), 0, W};
-        for (int s : part) {
-          S.small_list.push_back(s);
-          sc.mmax = std::max(sc.mmax, P.m[s]);
-          sc.flops += front_flops(P.m[s], P.w[s]);
-        }
-        lv.small.push_back(sc);
-      }
-      for (int q = 0; q < 4; q++) {
-        if (bucket[q].empty()) continue;
-        SmallClass sc{(int)S.small_list.size(), (int)bucket[q].size(), 0, 0};
-        for (int s : bucket[q]) {
-          S.small_list.push_back(s);
-          sc.mmax = std::max(sc.mmax, P.m[s]);
-          sc.flops += front_flops(P.m[s], P.w[s]);
-        }
-        lv.small.push_back(sc);
-      }
-    }
-    int maxw = 0;
-    for (int s : big) maxw = std::max(maxw, P.w[s]);
-    // Blocked path, one step per 64-column panel kb of every big front of the
-    // level (right-looking, look-ahead 1, Schur updates of depth 64):
-    //   first step  k_panel_first: the front's first diagonal tile factored +
-    //               inverted, the rows below it solved (trsm) by workgroups that
-    //               wait for that inverse (in-launch hand-off)
-    //   each step   k_step: the next panel's diagonal tile updated with panel kb,
-    //               factored and inverted (sdiag); the tiles below it in the
-    //               next panel's column block updated, then solved against that
-    //               inverse (col); the other trailing tiles updated (syrk:
-    //               inline, or a concurrent k_panel_syrk_lds / 128 launch)
-    // Look-ahead bookkeeping: applied[i][j] = the first panel column whose
-    // Schur update column j of big front i has not received yet (every task
-    // updates whole columns: rows from the column down).  A step's tasks must
-    // find their columns uniform; a violation drops the step's skip (below) or
-    // marks the plan invalid (schedule_error).
-    std::vector<std::vector<int>> applied(big.size());
-    for (size_t i = 0; i < big.size(); i++) applied[i].assign(P.m[big[i]], 0);
-    auto uniform = [&](size_t i, int c0, int c1, int k0) {
-      for (int j = c0; j < c1; j++)
-        if (applied[i][j] != k0) return false;
-      return true;
-    };
-    bool apart_chain = false;   // once a step's plain tiles go to their own launch, the later ones do too
-    // deferred far updates (apart steps at a kKB block end): per step and big
-    // front, the largest column its k_step tasks and near plain tiles touch
-    // (touch), and the first column of its far plain tiles (far0, m = none)
-    // far0[step][piece][front]: the far pieces are the far range cut at the kKB
-    // blocks (the update-matrix columns past w one piece), each joined on its own
-    std::vector<std::vector<int>> touch;
-    std::vector<std::vector<std::vector<int>>> far0;
-    for (int kb = 0; kb < maxw; kb += kNB) {
-      touch.emplace_back(big.size(), 0);
-      far0.emplace_back();
-      PanelStep ps;
-      ps.kb = kb;
-      ps.syrk_flops = ps.plain_flops = ps.step_flops = ps.first_flops = 0;
-      ps.col_off = (int)S.col_tasks.size();
-      ps.syrk_off = (int)S.syrk_tasks.size();
-      ps.potrf_off = (int)S.potrf_list.size();
-      ps.sdiag_off = (int)S.sdiag_tasks.size();
-      // first panel of a front: k_panel_first (diagonal + trsm waiters)
-      std::vector<int4> xfirst, xstep;   // distributed top: panels factored by the first / the step launch
-      for (int s : big) {
-        if (kb != 0 || P.w[s] <= 0) continue;
-        const int nb = std::min(kNB, P.w[s]), m = P.m[s];
-        if (dist) xfirst.push_back(make_int4(s, 0, nb, cowner(s, 0)));
-        if (!mine(s, 0)) continue;
-        S.potrf_list.push_back(s);
-        ps.first_flops += 2.0 * nb * nb * (double)nb / 3.0 + (double)std::max(0, m - nb) * nb * nb;
-      }
-      ps.potrf_cnt = (int)S.potrf_list.size() - ps.potrf_off;
-      for (int s : big)
-        if (kb == 0 && P.w[s] > 0 && mine(s, 0))
-          for (int r0 = kNB; r0 < P.m[s]; r0 += kNB) S.col_tasks.push_back(make_int4(s, r0, 0, -1));
-      ps.fcol_cnt = (int)S.col_tasks.size() - ps.col_off;
-      ps.xfirst = add_exchange(S, xfirst);
-      // this panel's Schur update, deferred by kKB-column blocks: inside a block
-      // only the block's remaining columns [kn, be) are updated ("inner", bit 31
-      // of k0: tasks clip columns at the block end); after the block's last
-      // panel the trailing columns [be, m) get the whole block's update.
-      // With the plain tiles in their own launch (apart) the column block the
-      // next step prepares, [kn + 64, kn + 128), is skipped: the next step's
-      // diagonal / column tasks apply this panel's update with their own
-      // (depth 2 panels, or the deferred block + 1 panel), so the next step
-      // does not wait for this step's plain tiles (joined one step later).
-      // The skip is a property of the front alone (its size), never of the
-      // level it sits in: the update grouping -- hence the rounding -- of a
-      // front is the same in every plan (the partitioned plans' fronts are bit
-      // for bit the one-rank plan's).
-      const bool lookahead = !getenv("PGO_NO_LOOKAHEAD");
-      const bool far_on = getenv("PGO_FAR") && atoi(getenv("PGO_FAR")) == 1;
-      // (PGO_LOOKAHEAD_M: the front height threshold, a test knob)
-      const int la_m = getenv("PGO_LOOKAHEAD_M") ? atoi(getenv("PGO_LOOKAHEAD_M")) : kLookaheadM;
-      auto front_skip = [&](int s) { return lookahead && P.m[s] >= la_m; };
-      // Prep (look-ahead fronts): the step also brings the column block after
-      // the next one, [kn + 64, kn + 128), up to date with the panels before kn
-      // (k_step workgroups beside the diagonal chain), so the next step's
-      // diagonal and column tasks apply one panel only; the plain tiles skip
-      // that block too.  Only for whole 64-column pivot blocks.
-      auto has_prep = [&](int s, int kn_) { return front_skip(s) && kn_ + 2 * kNB <= P.w[s]; };
-      auto plain_range = [&](int s, bool skip, int& cstart, int& cend) {
-        const int w = P.w[s], m = P.m[s], nb = std::min(kNB, w - kb), kn = kb + nb;
-        const int bs = kb & ~(kKB - 1), be = std::min(bs + kKB, w);
-        const bool inner = kn < be;
-        cend = inner ? be : m;
-        cstart = kn < w ? kn + kNB : kn;
-        if (skip && kn + kNB < w) {   // the next step prepares [kn2, kn2 + 64): only when it covers all of it
-          const int kn2 = kn + kNB, bs2 = kn & ~(kKB - 1), be2 = std::min(bs2 + kKB, w);
-          const int colend2 = kn2 < be2 ? be2 : m;
-          if (std::min(kn2 + kNB, colend2) == kn2 + kNB && cstart + kNB <= cend) {
-            cstart += kNB;
-            if (has_prep(s, kn2)) cstart += kNB;   // the next step's prep block
-          }
-        }
-      };
-      auto ntiles = [&](int T) {
-        long long cnt = 0;
-        for (int s : big) {
-          if (P.w[s] <= kb) continue;
-          int c0, c1;
-          plain_range(s, front_skip(s), c0, c1);
-          for (int cc = c0; cc < c1; cc += T) cnt += (P.m[s] - cc + T - 1) / T;
-        }
-        return cnt;
-      };
-      // plain tiles: 128x128 (LDS-pipelined kernel) when there are many rounds of
-      // them (measured: at <= ~500 tiles the 64x64 kernel's finer granularity
-      // wins, scripts/ubench_syrk.hip), else 64x64; few 64-tiles ride in k_step,
-      // many go to a concurrent launch (k_step's LDS request, sized for the
-      // diagonal workgroups, halves their occupancy)
-      // (PGO_BIGTILE_MIN: the 128-tile threshold, a tuning knob)
-      static const long long big_min = getenv("PGO_BIGTILE_MIN") ? atoll(getenv("PGO_BIGTILE_MIN")) : 4096;
-      const int tile0 = ntiles(kBigTile) >= big_min ? kBigTile : kTile;
-      const bool apart = apart_chain || !(tile0 == kTile && ntiles(kTile) <= kInlineTiles);
-      std::vector<int4> plain;   // (front, first column, end column, k0): rows from the column down
-      // ... the far part of an apart step's plain range (a kKB block end: the
-      // columns past the next block, [be + kKB, m)): its own launch on a fourth
-      // stream, joined only before the first later step that touches them
-      std::vector<std::vector<int4>> plain_far;   // [piece]: the ranges of every front's piece g
-      std::vector<double> far_pflops;
-      std::vector<int4> prep;    // prep tiles (front, r0, c0, k0), whole 64x64 tiles
-      bool conflict = false;   // a front's next step reads this step's plain tiles
-      for (size_t i = 0; i < big.size(); i++) {
-        const int s = big[i];
-        if (P.w[s] <= kb) continue;
-        const int w = P.w[s], m = P.m[s];
-        const int nb = std::min(kNB, w - kb), kn = kb + nb;
-        const int bs = kb & ~(kKB - 1), be = std::min(bs + kKB, w);
-        const bool inner = kn < be;
-        const int colend = inner ? be : m;   // the device's column clip
-        if (kn < w) {   // next panel: its diagonal tile and the tiles below it
-          const int nb2 = std::min(kNB, w - kn), c1 = std::min(kn + kNB, colend);
-          const int k0 = applied[i][kn];
-          if (!uniform(i, kn, c1, k0)) {
-            if (getenv("PGO_SCHED_DEBUG") && !S.schedule_error)
-              fprintf(stderr, "sched: sdiag front %d w %d m %d kb %d cols [%d,%d) k0 %d\n", s, w, m, kb, kn, c1, k0);
-            S.schedule_error = true;
-          }
-          for (int j = kn; j < c1; j++) applied[i][j] = kn;
-          touch.back()[i] = std::max(touch.back()[i], c1);
-          const int depth = kn - k0, kw = inner ? (k0 | (int)0x80000000) : k0;
-          if (dist) xstep.push_back(make_int4(s, kn, nb2, cowner(s, kn)));
-          const bool own = mine(s, kn);
-          if (own) S.sdiag_tasks.push_back(make_int4(s, kn, kn, kw));
-          const double fd = (double)depth * kNB * (kNB + 1) + 2.0 * nb2 * nb2 * (double)nb2 / 3.0 +
-                            (double)std::min(kNB - nb2, m - kn - nb2) * nb2 * nb2;
-          ps.step_flops += fd;
-          ps.diag_flops += fd;
-          for (int r0 = kn + kNB; r0 < m; r0 += kNB) {
-            if (own) S.col_tasks.push_back(make_int4(s, r0, kn, kw));
-            const int rows = std::min(kNB, m - r0);
-            ps.step_flops += 2.0 * depth * rows * (c1 - kn) + (double)rows * nb2 * nb2;
-            ps.colupd_flops += 2.0 * depth * rows * (c1 - kn);
-            ps.trsm_flops += (double)rows * nb2 * nb2;
-          }
-          ps.syrk_flops += (double)depth * (c1 - kn) * (2.0 * m - kn - c1 + 1.0);
-        }
-        if (has_prep(s, kn)) {
-          const int b0 = kn + kNB, b1 = b0 + kNB, k0 = applied[i][b0];
-          if (!uniform(i, b0, b1, k0) || k0 > kb) {
-            if (getenv("PGO_SCHED_DEBUG") && !S.schedule_error)
-              fprintf(stderr, "sched: prep front %d w %d m %d kb %d cols [%d,%d) k0 %d\n", s, w, m, kb, b0, b1, k0);
-            S.schedule_error = true;
-          }
-          for (int j = b0; j < b1; j++) applied[i][j] = kn;
-          touch.back()[i] = std::max(touch.back()[i], b1);
-          if (mine(s, b0))
-            for (int r0 = b0; r0 < m; r0 += kNB) prep.push_back(make_int4(s, r0, b0, k0));
-          const double f = (double)(kn - k0) * kNB * (2.0 * m - b0 - b1 + 1.0);
-          ps.step_flops += f;
-          ps.colupd_flops += f;
-          ps.syrk_flops += f;
-        }
-        int cstart, cend;
-        plain_range(s, front_skip(s), cstart, cend);
-        // far split at a block end: columns past the next kKB block (the next
-        // steps touch none of them until that block ends)
-        // (PGO_FAR=1: measured within the replay noise on C3 -- 8.70 / 17.50 ms
-        // at 1 / 3 lanes with and without, profiles/r04c_ab_far.txt -- while
-        // the concurrent far tiles slow the k_step launches they overlap; off)
-        const int nend = (!inner && cstart < cend && far_on) ? std::max(cstart, std::min(cend, std::min(be + kKB, w)))
-                                                             : cend;
-        if (kn + kNB < w && cstart < nend) {   // the next step prepares [kn2, c2) of this front
-          const int kn2 = kn + kNB, bs2 = kn & ~(kKB - 1), be2 = std::min(bs2 + kKB, w);
-          const int c2 = std::min(kn2 + kNB, kn2 < be2 ? be2 : m);
-          if (cstart < c2 && kn2 < nend) conflict = true;   // this step's plain tiles feed it: lag 1
-        }
-        if (cstart < cend) {
-          int k0 = applied[i][cstart];
-          if (!uniform(i, cstart, cend, k0)) {
-            if (getenv("PGO_SCHED_DEBUG") && !S.schedule_error) {
-              fprintf(stderr, "sched: plain front %d w %d m %d kb %d cols [%d,%d) k0 %d:", s, w, m, kb, cstart, cend, k0);
-              for (int j = cstart; j < cend; j += 16) fprintf(stderr, " %d", applied[i][j]);
-              fprintf(stderr, "\n");
-            }
-            S.schedule_error = true;
-            k0 = kb;
-          }
-          for (int j = cstart; j < cend; j++) applied[i][j] = kn;
-          const int depth = kn - k0, kw = inner ? (k0 | (int)0x80000000) : k0;
-          for (int cc = cstart; cc < cend; cc++) ps.plain_flops += 2.0 * depth * (m - cc);
-          if (cstart < nend) plain.push_back(make_int4(s, cstart, nend, kw));
-          touch.back()[i] = std::max(touch.back()[i], nend);
-          for (int c0 = nend, g = 0; c0 < cend; g++) {   // far pieces: a kKB block each, [w, m) one
-            const int c1 = c0 < w ? std::min(std::min(cend, w), (c0 / kKB + 1) * kKB) : cend;
-            if ((int)plain_far.size() <= g) {
-              plain_far.emplace_back();
-              far_pflops.push_back(0.0);
-              far0.back().emplace_back(big.size(), 0);
-              for (size_t i2 = 0; i2 < big.size(); i2++) far0.back()[g][i2] = P.m[big[i2]];
-            }
-            plain_far[g].push_back(make_int4(s, c0, c1, kw));
-            far0.back()[g][i] = c0;
-            for (int cc = c0; cc < c1; cc++) far_pflops[g] += 2.0 * depth * (m - cc);
-            c0 = c1;
-          }
-        }
-      }
-      ps.syrk_flops += ps.plain_flops;
-      ps.sdiag_cnt = (int)S.sdiag_tasks.size() - ps.sdiag_off;
-      ps.col_cnt = (int)S.col_tasks.size() - ps.col_off - ps.fcol_cnt;
-      S.col_tasks.insert(S.col_tasks.end(), prep.begin(), prep.end());
-      ps.prep_cnt = (int)prep.size();
-      long long cnt128 = 0;
-      for (const int4& u : plain)
-        for (int c0 = u.y; c0 < u.z; c0 += kBigTile) cnt128 += (P.m[u.x] - c0 + kBigTile - 1) / kBigTile;
-      for (const auto& pl : plain_far)
-        for (const int4& u : pl)
-          for (int c0 = u.y; c0 < u.z; c0 += kBigTile) cnt128 += (P.m[u.x] - c0 + kBigTile - 1) / kBigTile;
-      // (distributed top: 64-wide tiles, split where the column owner changes;
-      // a tile's elements are computed alike in either kernel, so this is
-      // bitwise the 128-tile update)
-      ps.syrk_tile = cnt128 >= big_min && !dist ? kBigTile : kTile;
-      // A tile's columns stay inside one 64-column block of the packed front
-      // (pgo_chol.h front_packed): a range starting inside a block (the update
-      // matrix starts at w) opens with a narrow tile up to the block's end,
-      // clipped; a tile's elements are computed alike whatever its shape
-      auto gen_tiles = [&](const std::vector<int4>& ranges) {
-      for (const int4& u : ranges)
-        for (int c0 = u.y; c0 < u.z;) {
-          const int T = ps.syrk_tile;
-          const int ce = (c0 & 63) ? std::min(u.z, (c0 + 63) & ~63) : std::min(u.z, c0 + T);
-          // a tile narrower than T carries its width (the kernels clip its columns
-          // there): a block's end inside the range, or the range's end -- which
-          // is not the kernels' own column end where a step's range is split
-          // into near and far parts
-          const bool narrow = ce - c0 < T;
-          if (!dist) {
-            const int clip = narrow ? ce - c0 : 0;
-            for (int r0 = c0; r0 < P.m[u.x]; r0 += T) S.syrk_tasks.push_back(make_int4(u.x, r0 | (clip << kClipShift), c0, u.w));
-          } else {
-            for (int a = c0; a < ce;) {   // runs of one column owner: (a, b)
-              int b = a + 1;
-              while (b < ce && cowner(u.x, b) == cowner(u.x, a)) b++;
-              if (mine(u.x, a)) {
-                const int clip = (a == c0 && b == ce && !narrow) ? 0 : b - a;
-                for (int r0 = c0; r0 < P.m[u.x]; r0 += kTile)
-                  S.syrk_tasks.push_back(make_int4(u.x, r0 | (clip << kClipShift), a, u.w));
-              }
-              a = b;
-            }
-          }
-          c0 = ce;
-        }
-      };
-      gen_tiles(plain);
-      const int near_end = (int)S.syrk_tasks.size();
-      std::vector<int> piece_end;
-      for (const auto& pl : plain_far) {
-        gen_tiles(pl);
-        piece_end.push_back((int)S.syrk_tasks.size());
-      }
-      ps.syrk_cnt = (int)S.syrk_tasks.size() - ps.syrk_off;
-      ps.syrk_inline = !apart && ps.syrk_tile == kTile && ps.syrk_cnt <= kInlineTiles;
-      ps.far_cnt = ps.syrk_inline ? 0 : (int)S.syrk_tasks.size() - near_end;
-      auto xcd = [&](int b, int e) {   // XCD-aware order of a launch's Schur-update tiles
-        std::vector<int4> mine(S.syrk_tasks.begin() + b, S.syrk_tasks.begin() + e);
-        xcd_order(mine, ps.syrk_tile);
-        std::copy(mine.begin(), mine.end(), S.syrk_tasks.begin() + b);
-      };
-      if (ps.far_cnt == 0) {   // (inline, or nothing far: the far ranges' columns are this step's)
-        for (const auto& pl : plain_far)
-          for (const int4& u : pl)
-            for (size_t i = 0; i < big.size(); i++)
-              if (big[i] == u.x) touch.back()[i] = std::max(touch.back()[i], u.z);
-        far0.back().clear();
-        xcd(ps.syrk_off, ps.syrk_off + ps.syrk_cnt);
-      } else {
-        xcd(ps.syrk_off, near_end);
-        ps.far_p0 = (int)lv.far_pieces.size();
-        int b = near_end;
-        for (size_t g = 0; g < plain_far.size(); g++) {   // (piece: first tile relative to syrk_off, count)
-          xcd(b, piece_end[g]);
-          lv.far_pieces.push_back(make_int4((int)lv.panels.size(), b - ps.syrk_off, piece_end[g] - b, -1));
-          lv.far_piece_flops.push_back(far_pflops[g]);   // (a piece may hold no tile of this rank)
-          ps.far_flops += far_pflops[g];
-          b = piece_end[g];
-        }
-        ps.far_np = (int)lv.far_pieces.size() - ps.far_p0;
-      }
-      // an apart launch no front's next step reads is joined before the step after next
-      ps.plain_lag = ps.syrk_cnt > 0 && !ps.syrk_inline ? (conflict ? 1 : 2) : 0;
-      // (an inline plain after a lag-2 apart one could touch its tiles at once)
-      apart_chain = apart_chain || (ps.plain_lag == 2);
-      if (ps.syrk_inline) ps.step_flops += ps.plain_flops;
-      ps.xstep = add_exchange(S, xstep);
-      lv.panels.push_back(ps);
-    }
-    // a far piece is joined before the first later step whose k_step tasks or
-    // near plain tiles touch one of its columns (-1: at the level's end)
-    for (size_t q = 0; q < lv.far_pieces.size(); q++) {
-      int4& fp = lv.far_pieces[q];
-      const int j = fp.x, g = (int)q - lv.panels[j].far_p0;
-      const std::vector<int>& f0 = far0[j][g];
-      fp.w = -1;
-      for (size_t j2 = j + 1; j2 < lv.panels.size() && fp.w < 0; j2++)
-        for (size_t i = 0; i < big.size(); i++)
-          if (touch[j2][i] > f0[i]) {
-            fp.w = (int)j2;
-            break;
-          }
-    }
-    if (dist) {   // update columns past a front's last whole panel, factored with it: to every rank
-      std::vector<int4> tails;
-      for (int s : big) {
-        const int w = P.w[s], wr = std::min(P.m[s], (w + kNB - 1) / kNB * kNB);
-        if (wr > w) tails.push_back(make_int4(s, w, (wr - w) | (1 << 16), cowner(s, w)));
-      }
-      lv.xtail = add_exchange(S, tails);
-    }
-    // every column has its updates: pivot columns up to their panel, the
-    // trailing ones from every panel
-    for (size_t i = 0; i < big.size(); i++) {
-      const int s = big[i], w = P.w[s];
-      for (int j = 0; j < P.m[s]; j++)
-        if (applied[i][j] != (j < w ? (j / kNB) * kNB : w)) {
-          if (getenv("PGO_SCHED_DEBUG") && !S.schedule_error)
-            fprintf(stderr, "sched: end front %d w %d m %d col %d applied %d\n", s, w, P.m[s], j, applied[i][j]);
-          S.schedule_error = true;
-        }
-    }
-  };
-  // the level lists keep their storage from one schedule to the next in the
-  // plan (a live plan refresh rebuilds them all: fresh allocations cost it the
-  // page faults of ~tens of MB); chol_free releases them with the plan
-  if (!P.sched_scratch.p) P.sched_scratch.p = std::make_shared<std::vector<LevelLists>>();
-  std::vector<LevelLists>& out = *static_cast<std::vector<LevelLists>*>(P.sched_scratch.p.get());
-  if ((int)out.size() < nl) out.resize(nl);
-  for (int L = 0; L < nl; L++) out[L].reset();
-  std::vector<double> lms(2 * nl, 0.0);
-  plan_parallel(2 * nl, [&](int t) {
-    const auto t0 = std::chrono::steady_clock::now();
-    schedule_level(t >> 1, out[t >> 1], t & 1);
-    lms[t] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  });
-  if (timing) {
-    for (int L = 0; L < nl; L++)
-      fprintf(stderr, "  level %d: %.2f + %.2f ms (%zu fronts)\n", L, lms[2 * L], lms[2 * L + 1], bylevel[L].size());
-    phase("levels");
-  }
-  // Fused update-matrix tiles (pgo_chol.h syrk_gather), once both parts of a
-  // level are there.  A tile (ti, tj) of a blocked front with 64 tj >= w rounded
-  // up to 64 holds no H entry (chol_assembly checks it).  Its columns' first
-  // Schur update is the task that finds applied == 0 and is not inner: k0 word
-  // 0.  Where that is a 64-tile task of a front that is not distributed, the
-  // task takes the tile's child rectangles and the tile leaves the assembly
-  // list; its pairs stay in ea_pairs.  Such a task (r0, c0) is assembly tile
-  // (r0 / 64, c0 / 64) exactly: gen_tiles aligns a range's tiles to the
-  // 64-column blocks after a narrow opening tile (the block straddling w: not
-  // fused), rows run from the column down in steps of 64, and the range ends
-  // at m.  Asserted here (schedule_error).  A later update of the same columns
-  // (a wide front's next kKB block end: k0 > 0) stays a plain read-modify-write,
-  // and so does every tile of a 128-tile step.  Then the XCD order of what is
-  // left, as before (PGO_FUSE_UPDATE=0: all of it).
-  const bool fuse_on = !(getenv("PGO_FUSE_UPDATE") && atoi(getenv("PGO_FUSE_UPDATE")) == 0);
-  auto fuse_level = [&](int L, LevelLists& S) {
-    CholLevel& lv = P.levels[L];
-    const bool dist = dtop && L >= P.split;
-    const size_t e0 = (size_t)lv.ea_off.back();
-    S.syrk_gather.assign(S.syrk_tasks.size(), make_int2(-1, 0));
-    if (fuse_on && !dist && !S.syrk_tasks.empty()) {
-      // a front's tile tasks: contiguous from its tile (0, 0), tile (ti, tj) at ti (ti + 1) / 2 + tj
-      std::vector<std::pair<int, int>> fstart;
-      for (size_t q = e0; q < S.ea_tasks.size(); q++)
-        if (S.ea_tasks[q].y == 0) fstart.emplace_back(S.ea_tasks[q].x, (int)q);
-      std::sort(fstart.begin(), fstart.end());
-      std::vector<char> gone(S.ea_tasks.size(), 0);
-      // (elements of a child rectangle inside the child's lower triangle, as level_at_bytes counts them)
-      auto G = [](long long x, long long c) -> long long {
-        if (x <= 0) return 0;
-        return x <= c ? x * (x + 1) / 2 : c * (c + 1) / 2 + (x - c) * c;
-      };
-      for (PanelStep& ps : lv.panels) {
-        if (ps.syrk_tile != kTile) continue;
-        for (int q = ps.syrk_off; q < ps.syrk_off + ps.syrk_cnt; q++) {
-          const int4 t = S.syrk_tasks[q];
-          const int s = t.x, r0 = t.y & kRowMask, clip = t.y >> kClipShift, c0 = t.z, m = P.m[s];
-          if (t.w != 0 || c0 < ((P.w[s] + 63) & ~63)) continue;
-          const auto it = std::lower_bound(fstart.begin(), fstart.end(), std::make_pair(s, 0));
-          const int ti = r0 >> 6, tj = c0 >> 6;
-          const size_t e = it == fstart.end() ? S.ea_tasks.size() : (size_t)it->second + (size_t)ti * (ti + 1) / 2 + tj;
-          const bool whole = !(r0 & 63) && !(c0 & 63) && std::min(m, c0 + (clip ? clip : kTile)) == std::min(m, c0 + 64);
-          if (!whole || e >= S.ea_tasks.size() || S.ea_tasks[e].x != s || S.ea_tasks[e].y != ((ti << 16) | tj) || gone[e]) {
-            if (getenv("PGO_SCHED_DEBUG") && !S.schedule_error)
-              fprintf(stderr, "sched: fused tile front %d w %d m %d task (%d, %d) clip %d\n", s, P.w[s], m, r0, c0, clip);
-            S.schedule_error = true;
-            continue;
-          }
-          gone[e] = 1;
-          for (int k = 0; k < S.ea_tasks[e].w; k++) {
-            const int4 pr = S.ea_pairs[S.ea_tasks[e].z + k];
-            const long long nr = pr.w & 0xff, ncl = pr.w >> 8, d = pr.y - pr.z + 1;
-            ps.gather_bytes += 8.0 * (double)(G(d + nr - 1, ncl) - G(d - 1, ncl));
-          }
-          S.syrk_gather[q] = make_int2(S.ea_tasks[e].z, S.ea_tasks[e].w);
-          S.fused++;
-          S.fused_with_pairs += S.ea_tasks[e].w > 0;
-          S.fused_multipass += S.ea_tasks[e].w > 16;   // (kAsmPairs rectangles per gather pass)
-          S.fused_edge += r0 + 64 > m || c0 + 64 > m;
-        }
-      }
-      size_t o = e0;
-      for (size_t q = e0; q < S.ea_tasks.size(); q++)
-        if (!gone[q]) S.ea_tasks[o++] = S.ea_tasks[q];
-      S.ea_tasks.resize(o);
-    }
-    ea_xcd_order(S.ea_tasks, e0);
-    lv.ea_cnt.push_back((int)S.ea_tasks.size() - lv.ea_off.back());
-  };
-  plan_parallel(nl, [&](int L) { fuse_level(L, out[L]); });
-  phase("fuse");
-  // merge: level-relative offsets and indices made absolute; the level lists
-  // copied into place level by level on the pool (offsets from a serial pass)
-  struct Base {
-    size_t small_list, level_fronts, potrf_list, syrk_tasks, sdiag_tasks, col_tasks, bwd_tasks, bwdc_tasks, bwd_pref,
-        bwd_part_tasks, ea_tasks, ea_pairs, xchg, xp_tasks, xp_loff, xp_lstride;
-    int npart;
-  };
-  std::vector<Base> base(nl + 1);
-  {
-    Base z{};
-    for (int L = 0; L < nl; L++) {
-      const LevelLists& S = out[L];
-      base[L] = z;
-      z.small_list += S.small_list.size();
-      z.level_fronts += S.level_fronts.size();
-      z.potrf_list += S.potrf_list.size();
-      z.syrk_tasks += S.syrk_tasks.size();
-      z.sdiag_tasks += S.sdiag_tasks.size();
-      z.col_tasks += S.col_tasks.size();
-      z.bwd_tasks += S.bwd_tasks.size();
-      z.bwdc_tasks += S.bwdc_tasks.size();
-      z.bwd_pref += S.bwd_pref.size();
-      z.bwd_part_tasks += S.bwd_part_tasks.size();
-      z.ea_tasks += S.ea_tasks.size();
-      z.ea_pairs += S.ea_pairs.size();
-      z.xchg += S.xchg.size();
-      z.xp_tasks += S.xp_tasks.size();
-      z.xp_loff += S.xp_loff.size();
-      z.xp_lstride += S.xp_lstride.size();
-      z.npart += S.npart;
-    }
-    base[nl] = z;
-  }
-  const Base& tot = base[nl];
-  resize_room(P.small_list, tot.small_list);
-  resize_room(P.level_fronts, tot.level_fronts);
-  resize_room(P.potrf_list, tot.potrf_list);
-  resize_room(P.syrk_tasks, tot.syrk_tasks);
-  resize_room(P.syrk_gather, tot.syrk_tasks);
-  resize_room(P.sdiag_tasks, tot.sdiag_tasks);
-  resize_room(P.col_tasks, tot.col_tasks);
-  resize_room(P.bwd_tasks, tot.bwd_tasks);
-  resize_room(P.bwdc_tasks, tot.bwdc_tasks);
-  resize_room(P.bwd_pref, tot.bwd_pref);
-  resize_room(P.bwd_part_tasks, tot.bwd_part_tasks);
-  resize_room(P.ea_tasks, tot.ea_tasks);
-  resize_room(P.ea_pairs, tot.ea_pairs);
-  P.xchg.resize(tot.xchg);
-  resize_room(P.xp_tasks, tot.xp_tasks);
-  resize_room(P.xp_loff, tot.xp_loff);
-  resize_room(P.xp_lstride, tot.xp_lstride);
-  P.npart = tot.npart;
-  plan_parallel(nl, [&](int L) {
-    LevelLists& S = out[L];
-    CholLevel& lv = P.levels[L];
-    const Base& b = base[L];
-    const int bx = (int)b.xchg, npart0 = b.npart;
-    lv.front_off += (int)b.level_fronts;
-    lv.bwd_part.off += (int)b.bwd_part_tasks;
-    for (int4& t : S.bwd_part_tasks) t.w += npart0;
-    for (int q = lv.bwd[0].off; q < lv.bwd[0].off + lv.bwd[0].cnt; q++) S.bwd_pref[q].x += npart0;   // init tasks
-    for (SolveStep& st : lv.bwd) st.off += (int)b.bwd_tasks;
-    lv.bwdc.off += (int)b.bwdc_tasks;
-    for (int& o : lv.ea_off) o += (int)b.ea_tasks;
-    for (int4& t : S.ea_tasks) t.z += (int)b.ea_pairs;
-    for (int2& g : S.syrk_gather)
-      if (g.x >= 0) g.x += (int)b.ea_pairs;
-    for (SmallClass& sc : lv.small) sc.off += (int)b.small_list;
-    for (PanelStep& ps : lv.panels) {
-      ps.potrf_off += (int)b.potrf_list;
-      ps.col_off += (int)b.col_tasks;
-      ps.syrk_off += (int)b.syrk_tasks;
-      ps.sdiag_off += (int)b.sdiag_tasks;
-      if (ps.xfirst >= 0) ps.xfirst += bx;
-      if (ps.xstep >= 0) ps.xstep += bx;
-    }
-    if (lv.xtail >= 0) lv.xtail += bx;
-    for (XExchange& x : S.xchg) x.off += (int)b.xp_tasks;
-    auto put = [](auto& dst, size_t at, const auto& src) { std::copy(src.begin(), src.end(), dst.begin() + at); };
-    put(P.small_list, b.small_list, S.small_list);
-    put(P.level_fronts, b.level_fronts, S.level_fronts);
-    put(P.potrf_list, b.potrf_list, S.potrf_list);
-    put(P.syrk_tasks, b.syrk_tasks, S.syrk_tasks);
-    put(P.syrk_gather, b.syrk_tasks, S.syrk_gather);
-    put(P.sdiag_tasks, b.sdiag_tasks, S.sdiag_tasks);
-    put(P.col_tasks, b.col_tasks, S.col_tasks);
-    put(P.bwd_tasks, b.bwd_tasks, S.bwd_tasks);
-    put(P.bwdc_tasks, b.bwdc_tasks, S.bwdc_tasks);
-    put(P.bwd_pref, b.bwd_pref, S.bwd_pref);
-    put(P.bwd_part_tasks, b.bwd_part_tasks, S.bwd_part_tasks);
-    put(P.ea_tasks, b.ea_tasks, S.ea_tasks);
-    put(P.ea_pairs, b.ea_pairs, S.ea_pairs);
-    put(P.xchg, b.xchg, S.xchg);
-    put(P.xp_tasks, b.xp_tasks, S.xp_tasks);
-    put(P.xp_loff, b.xp_loff, S.xp_loff);
-    put(P.xp_lstride, b.xp_lstride, S.xp_lstride);
-  });
-  P.syrk_flops = 0;
-  P.fused_tiles = P.fused_with_pairs = P.fused_multipass = P.fused_edge = 0;
-  for (int L = 0; L < nl; L++) {
-    P.fused_tiles += out[L].fused;
-    P.fused_with_pairs += out[L].fused_with_pairs;
-    P.fused_multipass += out[L].fused_multipass;
-    P.fused_edge += out[L].fused_edge;
-    for (const PanelStep& ps : P.levels[L].panels) P.syrk_flops += ps.plain_flops;
-    P.xp_rslot = std::max(P.xp_rslot, out[L].xp_rslot);
-    P.schedule_error = P.schedule_error || out[L].schedule_error;
-  }
-  phase("schedule");
-  selinv_schedule(P);
-  phase("selinv");
-  chol_assembly(P, row_ptr, slot_col);
-  phase("assembly");
-}
-
 void chol_analyze(CholPlan& P, int n, const std::vector<int>& row_ptr, const std::vector<int>& slot_col) {
-  // PGO_PLAN_TIMING: phase times of the analysis on stderr (diagnostics)
-  static const bool timing = getenv("PGO_PLAN_TIMING") != nullptr;
-  auto tlast = std::chrono::steady_clock::now();
-  auto phase = [&](const char* what) {
-    if (!timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "chol_analyze %-12s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tlast).count());
-    tlast = t;
-  };
+  PhaseTimer phase("chol_analyze");
   P.nslots = (long long)slot_col.size();
   P.n = n;
   // ---- pose adjacency (old index), unique, no self loops
@@ -1773,14 +671,7 @@ static void assembly_splice(CholPlan& P, const std::vector<int>& row_ptr, const 
 void chol_assembly(CholPlan& P, const std::vector<int>& row_ptr, const std::vector<int>& slot_col) {
   const int n = P.n, ns = P.ns;
   const int nth = std::max(1, std::min(plan_threads(), n));   // (the chunks over the n poses: one per thread)
-  static const bool timing = getenv("PGO_PLAN_TIMING") != nullptr;
-  auto tl = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "chol_assembly %-12s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tl).count());
-    tl = t;
-  };
+  PhaseTimer lap("chol_assembly");
   P.nslots = (long long)slot_col.size();
   const bool splice = P.asm_splice && P.asm_bound && !P.asm_ptr.empty();
   P.asm_splice = false;

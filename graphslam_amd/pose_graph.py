@@ -505,6 +505,15 @@ class PoseGraph:
         summary["levels_table"] = lv
         return summary
 
+    def debug_plan_digest(self, part_size=1, part_rank=0):
+        """Host-only: the digest of the Cholesky plan for rank `part_rank` of
+        `part_size`: (one 64-bit hash per section of the plan -- two plans are
+        the same exactly when all agree --, the counters of the scheduler's
+        branches the plan took)."""
+        out = np.zeros(64, np.uint64)
+        ns = self._check(self._L.pgo_debug_plan_digest(self._h, int(part_size), int(part_rank), L.u64ptr(out), 64))
+        return [int(v) for v in out[:ns]], [int(v) for v in out[ns:ns + 20]]
+
     def debug_selinv_plan(self, cap=4096):
         """Host-only summary of marginal_covariances_all's pass: launches,
         algorithmic flops, doubles of extra device workspace, levels, and the

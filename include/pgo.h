@@ -525,6 +525,15 @@ int pgo_debug_solve(pgo_graph *g, double lambda, const pgo_params *params, doubl
  * their front's edge; from out[16], 6 per level (leaves first):
  * fronts, max m, max 64-blocks, panel steps, small fronts, syrk tiles. */
 int pgo_debug_plan(pgo_graph *g, double *out, int cap);
+/* Host-only: the digest of the plan of the current graph for rank `part_rank`
+ * of `part_size` (1, 0: the one-rank plan), planned as pgo_debug_partition
+ * plans it.  Returns S, the number of sections; out[0..S) = one 64-bit FNV-1a
+ * hash per section of the plan (fronts and storage, partition and exchange
+ * layout, level records, factor task lists, solve task lists, assembly,
+ * selected inversion), then 20 counters of the scheduler's branches the plan
+ * took (csrc/pgo_plan_digest.h), filled up to cap.  Two plans are the same
+ * exactly when their sections agree. */
+int pgo_debug_plan_digest(pgo_graph *g, int part_size, int part_rank, uint64_t *out, int cap);
 
 /* Host-only: the selected-inversion pass of pgo_marginal_covariances_all as
  * the plan of the graph as it stands schedules it (cap >= 4).  out[0] kernel

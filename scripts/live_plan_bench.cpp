@@ -2,7 +2,7 @@
 // of an edge list's graph, then R registrations of one pose each (odometry to
 // the previous pose + one loop closure to an old pose), as bench.py's live line.
 //   hipcc -O2 -std=c++17 -I include scripts/live_plan_bench.cpp graphslam_amd/csrc/pgo_symbolic.cpp \
-//     graphslam_amd/csrc/pgo_order.cpp -o /tmp/live_plan_bench
+//     graphslam_amd/csrc/pgo_schedule.cpp graphslam_amd/csrc/pgo_order.cpp -o /tmp/live_plan_bench
 //   PGO_PLAN_TIMING=1 /tmp/live_plan_bench edges.bin n [R]
 #include <algorithm>
 #include <chrono>

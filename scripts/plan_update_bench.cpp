@@ -3,7 +3,7 @@
 // registrations of one pose each (odometry to the previous pose + one loop
 // closure to a random earlier pose), as bench.py's live_resolve.
 //   hipcc -O2 -std=c++17 scripts/plan_update_bench.cpp graphslam_amd/csrc/pgo_symbolic.cpp \
-//     graphslam_amd/csrc/pgo_order.cpp -o /tmp/plan_update_bench
+//     graphslam_amd/csrc/pgo_schedule.cpp graphslam_amd/csrc/pgo_order.cpp -o /tmp/plan_update_bench
 //   PGO_PLAN_TIMING=1 /tmp/plan_update_bench edges.bin n [registrations]
 #include <algorithm>
 #include <chrono>

@@ -1,7 +1,7 @@
 """Designed dense-front graphs: one pose graph per Cholesky front-kernel class.
 
 The multifrontal Cholesky picks its kernel per front from the front's pivot
-width w and height m (pgo_symbolic.cpp, "part 1: the factorisation lists";
+width w and height m (pgo_schedule.cpp, LevelCtx::small_classes;
 pgo_chol.h front_packed).  Nested dissection leaves little control over (w, m)
 on the benchmark graphs; on these graphs it leaves none to chance:
 
@@ -33,7 +33,7 @@ import numpy as np
 from graphslam_amd import datasets
 
 # ------------------------------------------------------------------ the rule
-# One statement of the rule in pgo_symbolic.cpp / pgo_chol.h (default knobs):
+# One statement of the rule in pgo_schedule.cpp / pgo_chol.h (default knobs):
 # a front is packed and takes the blocked path when m > 128 or w > 32; else one
 # wavefront factorises it, compiled for a panel of 8, 16 or 32 columns and for
 # one (m <= 64) or two (m <= 128) rows per lane.

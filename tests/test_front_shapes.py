@@ -81,7 +81,7 @@ def test_case_reaches_its_fronts(pg_cls, name):
 
 def test_front_class_rule():
     """front_class restates pgo_chol.h front_packed and the one-wavefront
-    classes of pgo_symbolic.cpp at every edge."""
+    classes of pgo_schedule.cpp at every edge."""
     fc = fs.front_class
     assert [fc(w, w) for w in (3, 8, 9, 16, 17, 32, 33)] == ["wave8_m64", "wave8_m64", "wave16_m64", "wave16_m64",
                                                               "wave32_m64", "wave32_m64", "blocked"]

@@ -4,7 +4,7 @@ A 64x64 tile of a blocked front's update matrix whose column block starts at
 or past w rounded up to 64 holds no H entry, only what the front's children
 extend-add into it.  Where its first Schur update is a 64-tile task, that task
 gathers the children's rectangles itself and the tile has no assembly task
-(pgo_chol.h syrk_gather, pgo_symbolic.cpp fuse_level, pgo_chol.hip
+(pgo_chol.h syrk_gather, pgo_schedule.cpp fuse_level, pgo_chol.hip
 syrk_lds_body).  Every element is the same sum in the same order, so the knob
 changes no bit of any result.
 
