@@ -185,6 +185,7 @@ def lib():
         "pgo_debug_lm_replay": (C.c_int, [C.POINTER(PgoParams), C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_int), dp, dp, dp, C.c_int, dp, C.c_int]),
         "pgo_debug_fronts": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+        "pgo_debug_row_lanes": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "pgo_closest_keyframe": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, u64p, dp]),
         "pgo_closest_keyframes": (C.c_int, [vp, C.c_size_t, u64p, C.c_int, u64p, dp]),
         "pgo_debug_search_ms": (C.c_int, [vp, dp, dp]),

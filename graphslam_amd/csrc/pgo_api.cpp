@@ -2320,6 +2320,16 @@ int pgo_debug_fronts(pgo_graph* g, int* w, int* m, int* level, int cap) {
   return P.ns;
 }
 
+int pgo_debug_row_lanes(pgo_graph* g, int* G, int* G1) {
+  if (!g || !G || !G1) return PGO_E_ARG;
+  RC_TRY(download_values(g));
+  pgo::GraphStructure H;   // the structure upload_structure would build (no plan, no device)
+  RC_TRY(build_structure(g, H));
+  *G = H.G;
+  *G1 = H.G1;
+  return PGO_OK;
+}
+
 int pgo_debug_plan(pgo_graph* g, double* out, int cap) {
   if (!g || !out || cap < 16) return PGO_E_ARG;
   pgo::GraphStructure H;

@@ -537,6 +537,13 @@ class PoseGraph:
                                                      lv.ctypes.data_as(ip), ns)))
         return w, m, lv
 
+    def debug_row_lanes(self):
+        """Host-only: (G, G1), the sub-group widths of the row kernels
+        (k_linearize / k_pcg_spmv / k_spmv / k_model_decrease; k_linearize_side1)."""
+        G, G1 = C.c_int(0), C.c_int(0)
+        self._check(self._L.pgo_debug_row_lanes(self._h, C.byref(G), C.byref(G1)))
+        return G.value, G1.value
+
     def debug_parents(self):
         """Host-only: the parent supernode of every supernode (-1: a root)."""
         ns = self._L.pgo_debug_fronts(self._h, None, None, None, 0)

@@ -597,6 +597,12 @@ int pgo_debug_ordering(pgo_graph *g, int32_t *perm, size_t n);
    (height in the elimination tree); returns the supernode count (arrays are
    filled up to cap entries) or a negative status */
 int pgo_debug_fronts(pgo_graph *g, int *w, int *m, int *level, int cap);
+/* Host-only, no device: the sub-group widths the row kernels of the graph as it
+   stands are instantiated with.  G (4, 8, 16 or 32 lanes per vertex row, from
+   the mean row length 2 E / n): k_linearize, k_pcg_spmv, k_spmv,
+   k_model_decrease; G1 (from the mean side-1 list length E / n):
+   k_linearize_side1. */
+int pgo_debug_row_lanes(pgo_graph *g, int *G, int *G1);
 
 #ifdef __cplusplus
 }
