@@ -46,6 +46,16 @@ PGO_LOSS_HUBER = 1
 PGO_LOSS_CAUCHY = 2
 PGO_LOSS_GEMAN_MCCLURE = 3
 LOSSES = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
+PGO_GNC_GM = 0
+PGO_GNC_TLS = 1
+GNC_LOSSES = {"gm": 0, "tls": 1}
+PGO_GNC_STOP_MU = 0
+PGO_GNC_STOP_COST = 1
+PGO_GNC_STOP_MAX_ITER = 2
+PGO_GNC_STOP_NO_CANDIDATES = 3
+PGO_GNC_STOP_ALL_INLIERS = 4
+PGO_GNC_STOP_ERROR = 5
+GNC_STOP_REASONS = {0: "mu", 1: "cost", 2: "max_iterations", 3: "no_candidates", 4: "all_inliers", 5: "error"}
 TRANSPORTS = {0: "none", 1: "rccl", 2: "host"}
 ABI_VERSION = 6
 STOP_REASONS = {0: "converged", 1: "lambda_upper_bound", 2: "max_iterations", 3: "max_outer", 4: "small_cost_change",
@@ -92,6 +102,22 @@ class PgoInitStats(C.Structure):
     _fields_ = [("status", C.c_int), ("components", C.c_int), ("tree_depth", C.c_int), ("wraps", C.c_longlong),
                 ("error_before", C.c_double), ("error_after", C.c_double), ("ms_total", C.c_double),
                 ("ms_tree", C.c_double), ("ms_orient", C.c_double), ("ms_trans", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class PgoGncParams(C.Structure):
+    _fields_ = [("loss", C.c_int), ("barc_sq", C.c_double), ("mu_step", C.c_double), ("max_iterations", C.c_int),
+                ("relative_cost_tol", C.c_double), ("weights_tol", C.c_double), ("keep_weights", C.c_int)]
+
+
+class PgoGncStats(C.Structure):
+    _fields_ = [("status", C.c_int), ("stop_reason", C.c_int), ("outer_iterations", C.c_int),
+                ("candidates", C.c_int), ("outliers", C.c_int), ("inner_tries", C.c_longlong),
+                ("linearizations", C.c_longlong), ("mu_initial", C.c_double), ("mu_final", C.c_double),
+                ("initial_error", C.c_double), ("final_cost", C.c_double), ("ms_total", C.c_double),
+                ("ms_inner", C.c_double), ("ms_weights", C.c_double)]
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
@@ -158,6 +184,16 @@ def lib():
         "pgo_add_edges_robust": (C.c_int, [vp, C.c_size_t, u64p, u64p, dp, dp, C.c_int, C.POINTER(C.c_int), dp,
                                            C.c_int]),
         "pgo_get_edge_weights": (C.c_int, [vp, C.c_size_t, C.c_size_t, dp]),
+        "pgo_set_edge_weights": (C.c_int, [vp, C.c_size_t, C.c_size_t, dp]),
+        "pgo_gnc_default_params": (None, [C.POINTER(PgoGncParams)]),
+        "pgo_optimize_gnc": (C.c_int, [vp, C.POINTER(PgoParams), C.POINTER(PgoGncParams), C.c_size_t,
+                                       C.POINTER(C.c_size_t), C.POINTER(PgoGncStats)]),
+        "pgo_get_gnc_trace": (C.c_int, [vp, dp, C.c_int]),
+        "pgo_debug_gnc_control": (C.c_int, [C.POINTER(PgoGncParams), C.c_double, C.c_int, dp, dp, dp, dp,
+                                            C.POINTER(C.c_int)]),
+        "pgo_debug_gnc_weight": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_size_t, dp, dp]),
+        "pgo_debug_gnc_sweep": (C.c_int, [vp, C.c_int, C.c_double, C.c_double, C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.c_int, dp, dp]),
         "pgo_optimize": (C.c_int, [vp, C.POINTER(PgoParams), C.POINTER(PgoStats)]),
         "pgo_get_pose": (C.c_int, [vp, C.c_uint64, dp]),
         "pgo_get_poses": (C.c_int, [vp, C.c_size_t, u64p, dp]),

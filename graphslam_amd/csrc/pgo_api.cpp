@@ -27,6 +27,7 @@
 #include "pgo_comm.h"
 #include "pgo_search.h"
 #include "pgo_device.h"
+#include "pgo_gnc.h"
 #include "pgo_init.h"
 #include "pgo_lm.h"
 #include "pgo_structure.h"
@@ -64,6 +65,7 @@ struct pgo_graph {
   std::vector<unsigned char> eloss;         // loss kind per between factor (PGO_LOSS_*)
   std::vector<double> ek;                   // ... and its parameter k (1 with PGO_LOSS_NONE)
   size_t n_robust = 0;                      // factors with a loss other than NONE: any -> the robust kernels
+  size_t n_fixed = 0;                       // ... of which fixed weights below 1 (pgo::kLossFixed, ek the weight)
   std::vector<uint64_t> pk;
   std::vector<double> pz, pom;
   // ---- device state ----
@@ -154,6 +156,11 @@ struct pgo_graph {
   // ---- linear initialisation (pgo_initialize_linear) ----
   double* init_tgt = nullptr;               // [ne + np] the stages' angle targets, device factor / prior order
   size_t init_tgt_cap = 0;
+  // ---- graduated non-convexity (pgo_optimize_gnc) ----
+  unsigned char* gnc_cand = nullptr;        // [cap_ne] 1: the device factor is a candidate (built per call)
+  double4* gnc_pose = nullptr;              // [cap_n] the values before an inner solve (put back if it fails)
+  size_t gnc_cand_cap = 0, gnc_pose_cap = 0;   // sized with the graph's capacity, freed with the device graph
+  std::vector<double> gnc_trace;            // per inner solve of the last pgo_optimize_gnc (kGncTraceCols each)
 };
 
 namespace {
@@ -273,6 +280,11 @@ void free_device(pgo_graph* g, bool keep_plan = false) {
                   d.erow, d.brow, d.s1_ptr, d.s1pos, d.eside, d.Dc, d.W, d.eloss, d.ek, d.s1fac, d.D, d.g, d.pose, d.pose_cand, d.pose_saved, d.x, d.r, d.z, d.p, d.q, d.Minv, d.part, d.scal, d.ctrl};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  if (g->gnc_cand) (void)hipFree(g->gnc_cand);
+  if (g->gnc_pose) (void)hipFree(g->gnc_pose);
+  g->gnc_cand = nullptr;
+  g->gnc_pose = nullptr;
+  g->gnc_cand_cap = g->gnc_pose_cap = 0;
   hipStream_t s = d.stream;
   d = DevGraph();
   d.stream = s;
@@ -2017,6 +2029,394 @@ int pgo_optimize(pgo_graph* g, const pgo_params* params, pgo_stats* stats) {
   if (stats) *stats = st;
   if (ctl.status < 0) return fail(g, ctl.status, pgo_status_string(ctl.status));
   return ctl.status;
+}
+
+// ---- fixed weights and graduated non-convexity (pgo_gnc.h / pgo_gnc.hip)
+
+namespace {
+
+constexpr int kGncTraceCols = 8;   // pgo_get_gnc_trace row
+
+// The host's loss kinds and parameters onto the device graph that is resident
+// (its first d.ne factors; appended ones travel with append_structure): the
+// loss arrays are allocated when the first factor gets a loss or a weight below
+// 1 and released when the last one loses it, which switches the handle between
+// the Gaussian and the robust kernel sets.  Values only: no structure, plan or
+// captured graph depends on them.  Without a resident graph the next upload
+// carries the host arrays.
+int sync_device_losses(pgo_graph* g) {
+  if (!g->dev_complete || !g->hip_ready) return PGO_OK;
+  HIP_TRY(g, hipSetDevice(g->device));
+  DevGraph& d = g->d;
+  pgo::GraphStructure& S = g->gs;
+  const size_t ne = (size_t)d.ne;
+  const bool want = g->n_robust > 0;
+  if (!want) {
+    if (!d.eloss) return PGO_OK;
+    HIP_TRY(g, hipStreamSynchronize(d.stream));
+    (void)hipFree(d.eloss);
+    (void)hipFree(d.ek);
+    (void)hipFree(d.s1fac);
+    d.eloss = nullptr;
+    d.ek = nullptr;
+    d.s1fac = nullptr;
+    S.s1fac.clear();
+    return PGO_OK;
+  }
+  if (!d.eloss) {
+    S.s1fac.resize(ne);
+    for (size_t e = 0; e < ne; e++) S.s1fac[S.s1pos[e]] = (int)e;
+    unsigned char* dl = nullptr;
+    double* dk = nullptr;
+    int* df = nullptr;
+    const size_t ce = std::max<size_t>(g->cap_ne, ne);
+    hipError_t e = hipMalloc((void**)&dl, std::max<size_t>(ce, 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&dk, std::max<size_t>(ce, 1) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&df, std::max<size_t>(ce, 1) * sizeof(int));
+    if (e == hipSuccess && ne)
+      e = hipMemcpyAsync(df, S.s1fac.data(), ne * sizeof(int), hipMemcpyHostToDevice, d.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {
+      if (dl) (void)hipFree(dl);
+      if (dk) (void)hipFree(dk);
+      if (df) (void)hipFree(df);
+      S.s1fac.clear();
+      HIP_TRY(g, e);
+    }
+    d.eloss = dl;
+    d.ek = dk;
+    d.s1fac = df;
+  }
+  std::vector<unsigned char> hl;
+  std::vector<double> hk;
+  gather_losses(g, S.dorder.data(), ne, hl, hk);
+  RC_TRY(h2d(g, d.eloss, hl.data(), ne));
+  RC_TRY(h2d(g, d.ek, hk.data(), ne));
+  HIP_TRY(g, hipStreamSynchronize(d.stream));   // (the sources are locals)
+  return PGO_OK;
+}
+
+// host side of a fixed weight on user factor u (kind NONE or fixed before)
+void set_host_weight(pgo_graph* g, size_t u, double w) {
+  const bool was = g->eloss[u] == pgo::kLossFixed, is = w != 1.0;
+  g->eloss[u] = is ? (unsigned char)pgo::kLossFixed : (unsigned char)PGO_LOSS_NONE;
+  g->ek[u] = w;
+  if (is && !was) g->n_robust++, g->n_fixed++;
+  if (!is && was) g->n_robust--, g->n_fixed--;
+}
+
+double wall_ms_since(std::chrono::steady_clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// The candidates' bytes in device order (gnc_cand) and the values buffer, sized
+// with the graph's capacity.
+int gnc_upload_candidates(pgo_graph* g, const std::vector<size_t>& cand) {
+  DevGraph& d = g->d;
+  const size_t ne = (size_t)d.ne, ce = std::max<size_t>(g->cap_ne, ne), cn = std::max<size_t>(g->cap_n, d.n);
+  if (g->gnc_cand_cap < ce) {
+    if (g->gnc_cand) (void)hipFree(g->gnc_cand);
+    g->gnc_cand = nullptr;
+    g->gnc_cand_cap = 0;
+    RC_TRY(dev_alloc(g, &g->gnc_cand, ce));
+    g->gnc_cand_cap = ce;
+  }
+  if (g->gnc_pose_cap < cn) {
+    if (g->gnc_pose) (void)hipFree(g->gnc_pose);
+    g->gnc_pose = nullptr;
+    g->gnc_pose_cap = 0;
+    RC_TRY(dev_alloc(g, &g->gnc_pose, cn));
+    g->gnc_pose_cap = cn;
+  }
+  std::vector<unsigned char> user(ne, 0), dev(ne);
+  for (size_t u : cand) user[u] = 1;
+  for (size_t e = 0; e < ne; e++) dev[e] = user[(size_t)g->gs.dorder[e]];
+  RC_TRY(h2d(g, g->gnc_cand, dev.data(), ne));
+  HIP_TRY(g, hipStreamSynchronize(d.stream));
+  return PGO_OK;
+}
+
+// one sweep and its read-back: out5 as launch_gnc_weights
+int gnc_sweep(pgo_graph* g, int loss, double mu, double c2, double wtol, int write, double* out5) {
+  DevGraph& d = g->d;
+  HIP_TRY(g, pgo::launch_gnc_weights(d, d.pose, g->gnc_cand, loss, mu, c2, wtol, write, d.scal));
+  RC_TRY(sync_scalars(g, 5));
+  std::memcpy(out5, g->h_scal, 5 * sizeof(double));
+  return PGO_OK;
+}
+
+// the candidates idx[0..n) (NULL: all) as checked user indices
+int gnc_candidates(pgo_graph* g, size_t n, const size_t* idx, std::vector<size_t>& cand) {
+  const size_t ne = g->ek1.size();
+  cand.clear();
+  if (!idx) {
+    cand.resize(ne);
+    for (size_t e = 0; e < ne; e++) cand[e] = e;
+  } else {
+    std::vector<unsigned char> seen(ne, 0);
+    cand.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+      if (idx[i] >= ne) return fail(g, PGO_E_ARG, "gnc: candidate index past the last between factor");
+      if (seen[idx[i]]) return fail(g, PGO_E_ARG, "gnc: duplicate candidate index");
+      seen[idx[i]] = 1;
+      cand.push_back(idx[i]);
+    }
+  }
+  for (size_t u : cand)
+    if (g->eloss[u] != PGO_LOSS_NONE && g->eloss[u] != pgo::kLossFixed)
+      return fail(g, PGO_E_ARG, "gnc: a candidate factor has a robust loss");
+  return PGO_OK;
+}
+
+// the candidates' weights from the device (d.ek) into the host arrays
+int gnc_download_weights(pgo_graph* g, const std::vector<size_t>& cand) {
+  DevGraph& d = g->d;
+  const size_t ne = (size_t)d.ne;
+  std::vector<double> hk(ne);
+  if (ne) HIP_TRY(g, hipMemcpyAsync(hk.data(), d.ek, ne * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(g, hipStreamSynchronize(d.stream));
+  std::vector<size_t> dpos(ne);
+  for (size_t e = 0; e < ne; e++) dpos[(size_t)g->gs.dorder[e]] = e;
+  for (size_t u : cand) set_host_weight(g, u, hk[dpos[u]]);
+  return PGO_OK;
+}
+
+}  // namespace
+
+int pgo_set_edge_weights(pgo_graph* g, size_t first, size_t n, const double* w) {
+  if (!g || (n && !w)) return PGO_E_ARG;
+  const size_t ne = g->ek1.size();
+  if (first > ne || n > ne - first) return fail(g, PGO_E_ARG, "set_edge_weights: range past the last between factor");
+  for (size_t i = 0; i < n; i++) {
+    if (!(std::isfinite(w[i]) && w[i] >= 0.0 && w[i] <= 1.0))
+      return fail(g, PGO_E_ARG, "set_edge_weights: a weight must be finite and in [0, 1]");
+    if (g->eloss[first + i] != PGO_LOSS_NONE && g->eloss[first + i] != pgo::kLossFixed)
+      return fail(g, PGO_E_ARG, "set_edge_weights: factor " + std::to_string(first + i) + " has a robust loss");
+  }
+  if (n == 0) return PGO_OK;
+  for (size_t i = 0; i < n; i++) set_host_weight(g, first + i, w[i]);
+  return sync_device_losses(g);
+}
+
+int pgo_get_gnc_trace(const pgo_graph* g, double* out, int cap) {
+  if (!g || cap < 0 || (cap > 0 && !out)) return PGO_E_ARG;
+  const int rows = (int)(g->gnc_trace.size() / kGncTraceCols);
+  if (cap > 0 && rows > 0)
+    std::memcpy(out, g->gnc_trace.data(), sizeof(double) * kGncTraceCols * std::min(rows, cap));
+  return rows;
+}
+
+int pgo_optimize_gnc(pgo_graph* g, const pgo_params* inner, const pgo_gnc_params* gnc, size_t n, const size_t* idx,
+                     pgo_gnc_stats* stats) {
+  RoctxRange range_gnc("pgo_optimize_gnc");
+  if (!g || (n && !idx && n != g->ek1.size())) return PGO_E_ARG;
+  pgo_gnc_params gp;
+  if (gnc) gp = *gnc;
+  else pgo_gnc_default_params(&gp);
+  pgo_gnc_stats st;
+  std::memset(&st, 0, sizeof(st));
+  st.mu_initial = st.mu_final = NAN;
+  auto leave = [&](int rc) {
+    st.status = rc;
+    if (stats) *stats = st;
+    return rc;
+  };
+  if (!pgo::gnc_params_ok(gp)) return leave(fail(g, PGO_E_ARG, "gnc: bad parameters"));
+  if (g->comm.size > 1) return leave(fail(g, PGO_E_ARG, "gnc: one rank only (the handle has a communicator)"));
+  if (g->n_robust > g->n_fixed)
+    return leave(fail(g, PGO_E_ARG, "gnc: the graph has factors under a robust loss"));
+  std::vector<size_t> cand;
+  {
+    const int rc = gnc_candidates(g, n, idx, cand);
+    if (rc != PGO_OK) return leave(rc);
+  }
+  const auto T0 = std::chrono::steady_clock::now();
+  g->gnc_trace.clear();
+  st.candidates = (int)cand.size();
+  const double c2 = gp.barc_sq;
+  // the candidates' weights: all 1 on the host (kind NONE), then the device
+  auto all_one = [&]() -> int {
+    for (size_t u : cand) set_host_weight(g, u, 1.0);
+    return sync_device_losses(g);
+  };
+  pgo_stats is;
+  auto row = [&](double mu, double cost, double sw, double nonbin, double rmax) {
+    const double r[kGncTraceCols] = {mu,   cost, sw, nonbin, rmax, (double)is.inner_iterations, (double)is.iterations,
+                                     (double)is.stop_reason};
+    g->gnc_trace.insert(g->gnc_trace.end(), r, r + kGncTraceCols);
+  };
+  auto inner_solve = [&]() -> int {
+    const auto t = std::chrono::steady_clock::now();
+    std::memset(&is, 0, sizeof(is));
+    const int rc = pgo_optimize(g, inner, &is);
+    st.ms_inner += wall_ms_since(t);
+    st.inner_tries += is.inner_iterations;
+    st.linearizations += is.linearizations;
+    return rc;
+  };
+  auto finish = [&](int rc) {
+    st.ms_total = wall_ms_since(T0);
+    return leave(rc);
+  };
+  {
+    const int rc = all_one();
+    if (rc != PGO_OK) return finish(rc);
+  }
+  // row 0: exactly pgo_optimize(g, inner)
+  {
+    const int rc = inner_solve();
+    st.initial_error = is.initial_error;
+    st.final_cost = is.final_error;
+    if (rc < 0) {
+      st.stop_reason = PGO_GNC_STOP_ERROR;
+      return finish(rc);
+    }
+  }
+  if (cand.empty()) {
+    row(NAN, is.final_error, 0.0, 0.0, 0.0);
+    st.stop_reason = PGO_GNC_STOP_NO_CANDIDATES;
+    return finish(PGO_OK);
+  }
+  HIP_TRY(g, hipSetDevice(g->device));
+  DevGraph& d = g->d;
+  // the candidates become fixed weights (1 so far): the robust kernel set from here on
+  for (size_t u : cand) {
+    if (g->eloss[u] != pgo::kLossFixed) g->n_robust++, g->n_fixed++;
+    g->eloss[u] = (unsigned char)pgo::kLossFixed;
+    g->ek[u] = 1.0;
+  }
+  // on any way out: the host arrays in step with what the call leaves behind
+  auto settle = [&](bool keep) -> int {
+    if (keep) RC_TRY(gnc_download_weights(g, cand));
+    else
+      for (size_t u : cand) set_host_weight(g, u, 1.0);
+    return sync_device_losses(g);
+  };
+  auto bail = [&](int rc) {
+    (void)settle(false);
+    st.stop_reason = PGO_GNC_STOP_ERROR;
+    return finish(rc);
+  };
+  {
+    int rc = sync_device_losses(g);
+    if (rc == PGO_OK) rc = gnc_upload_candidates(g, cand);
+    if (rc != PGO_OK) return bail(rc);
+  }
+  double s5[5];
+  auto sweep = [&](double mu, int write) -> int {
+    const auto t = std::chrono::steady_clock::now();
+    const int rc = gnc_sweep(g, gp.loss, mu, c2, gp.weights_tol, write, s5);
+    st.ms_weights += wall_ms_since(t);
+    return rc;
+  };
+  pgo::GncControl ctl(gp);
+  {
+    const int rc = sweep(1.0, 0);   // (read-only: the mu does not matter to the largest r^2)
+    if (rc != PGO_OK) return bail(rc);
+  }
+  row(NAN, is.final_error, (double)cand.size(), 0.0, s5[0]);
+  const bool iterate = ctl.start(is.final_error, s5[0]);
+  st.mu_initial = ctl.mu_initial;
+  if (iterate) {
+    for (;;) {
+      const double mu = ctl.mu;
+      int rc = sweep(mu, 1);
+      if (rc != PGO_OK) return bail(rc);
+      const double rmax = s5[0], sw = s5[1], nonbin = s5[2];
+      if (d.n) {
+        const hipError_t e = hipMemcpyAsync(g->gnc_pose, d.pose, d.n * sizeof(double4), hipMemcpyDeviceToDevice, d.stream);
+        if (e != hipSuccess) return bail(fail(g, PGO_E_HIP, hipGetErrorString(e)));
+      }
+      rc = inner_solve();
+      if (rc < 0) {   // the values of the last successful inner solve, the candidates plain again
+        const std::string why = g->last_error;
+        if (d.n && g->dev_structure && d.pose) {
+          (void)hipMemcpyAsync(d.pose, g->gnc_pose, d.n * sizeof(double4), hipMemcpyDeviceToDevice, d.stream);
+          (void)hipStreamSynchronize(d.stream);
+          g->dev_values = true;
+          g->host_values = false;
+        }
+        (void)settle(false);
+        g->last_error = why;
+        st.stop_reason = PGO_GNC_STOP_ERROR;
+        return finish(rc);
+      }
+      st.final_cost = is.final_error;
+      st.mu_final = mu;
+      row(mu, is.final_error, sw, nonbin, rmax);
+      if (!ctl.step(is.final_error, nonbin)) break;
+    }
+  }
+  st.outer_iterations = ctl.outer;
+  st.stop_reason = ctl.stop_reason;
+  {
+    const int rc = sweep(std::isfinite(ctl.mu) ? ctl.mu : 1.0, 0);   // r^2 > c^2 at the final values
+    if (rc != PGO_OK) return bail(rc);
+    st.outliers = (int)s5[3];
+  }
+  {
+    const int rc = settle(gp.keep_weights != 0);
+    if (rc != PGO_OK) return finish(rc);
+  }
+  return finish(ctl.stop_reason == PGO_GNC_STOP_MAX_ITER ? PGO_W_MAXITER : PGO_OK);
+}
+
+int pgo_debug_gnc_sweep(pgo_graph* g, int loss, double mu, double barc_sq, size_t n, const size_t* idx, int write,
+                        double* w_all, double* stats5) {
+  if (!g || !stats5 || (loss != PGO_GNC_GM && loss != PGO_GNC_TLS) || !(barc_sq > 0.0) || !(mu > 0.0) ||
+      !std::isfinite(mu) || !std::isfinite(barc_sq) || (n && !idx && n != g->ek1.size()))
+    return PGO_E_ARG;
+  if (g->n_robust > g->n_fixed) return fail(g, PGO_E_ARG, "gnc: the graph has factors under a robust loss");
+  std::vector<size_t> cand;
+  RC_TRY(gnc_candidates(g, n, idx, cand));
+  RC_TRY(ensure_device(g));
+  HIP_TRY(g, hipSetDevice(g->device));
+  const size_t ne = g->ek1.size();
+  // the candidates as fixed weights (their own, or 1) while the sweep runs
+  const std::vector<unsigned char> loss0 = g->eloss;
+  const std::vector<double> k0 = g->ek;
+  const size_t nr0 = g->n_robust, nf0 = g->n_fixed;
+  for (size_t u : cand) {
+    if (g->eloss[u] != pgo::kLossFixed) g->n_robust++, g->n_fixed++, g->ek[u] = 1.0;
+    g->eloss[u] = (unsigned char)pgo::kLossFixed;
+  }
+  auto restore = [&]() {
+    g->eloss = loss0;
+    g->ek = k0;
+    g->n_robust = nr0;
+    g->n_fixed = nf0;
+    return sync_device_losses(g);
+  };
+  int rc = cand.empty() ? PGO_OK : sync_device_losses(g);
+  if (rc == PGO_OK) rc = gnc_upload_candidates(g, cand);
+  if (rc == PGO_OK && cand.empty()) {   // nothing marked: no loss arrays needed, nothing to write
+    std::memset(stats5, 0, 5 * sizeof(double));
+    if (w_all) std::fill(w_all, w_all + ne, 1.0);
+    return restore();
+  }
+  if (rc == PGO_OK) rc = gnc_sweep(g, loss, mu, barc_sq, 1e-4, 1, stats5);
+  std::vector<double> hk(ne);
+  if (rc == PGO_OK && ne) {
+    hipError_t e = hipMemcpyAsync(hk.data(), g->d.ek, ne * sizeof(double), hipMemcpyDeviceToHost, g->d.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->d.stream);
+    if (e != hipSuccess) rc = fail(g, PGO_E_HIP, hipGetErrorString(e));
+  }
+  if (rc != PGO_OK) {
+    (void)restore();
+    return rc;
+  }
+  if (w_all) {
+    std::fill(w_all, w_all + ne, 1.0);
+    std::vector<unsigned char> is_cand(ne, 0);
+    for (size_t u : cand) is_cand[u] = 1;
+    for (size_t e = 0; e < ne; e++) {
+      const size_t u = (size_t)g->gs.dorder[e];
+      if (is_cand[u]) w_all[u] = hk[e];
+    }
+  }
+  if (!write) return restore();
+  RC_TRY(gnc_download_weights(g, cand));
+  return sync_device_losses(g);   // (a weight of exactly 1 is a plain factor again, on the device too)
 }
 
 int pgo_closest_keyframe(pgo_graph* g, double x, double y, int skip, uint64_t* key, double* dist) {

@@ -29,6 +29,12 @@ namespace pgo {
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 1024;   // partial-sum arrays are sized for this
 
+// Internal loss kind beside PGO_LOSS_* (0..3): a fixed weight, held in ek
+// (pgo_set_edge_weights; the candidates of pgo_optimize_gnc while it runs).
+// robust_weight returns ek, robust_rho 0.5 ek r^2.  pgo_add_edge_robust
+// rejects it.
+constexpr int kLossFixed = 4;
+
 struct DevGraph {
   int n = 0, ne = 0, np = 0, nslots = 0;
   int G = 8;                      // lanes per row (sub-group) for row kernels
@@ -71,9 +77,10 @@ struct DevGraph {
   double* scal = nullptr;         // [16] device scalars
   int* ctrl = nullptr;            // [4]: done flag, PCG iterations
   hipStream_t stream = nullptr;
-  // robust losses on between factors (null on an all-Gaussian graph, which then
-  // launches the Gaussian kernels only): kind PGO_LOSS_* and parameter k per
-  // factor in device order, and the inverse of s1pos
+  // robust losses and fixed weights on between factors (null on an all-Gaussian
+  // graph at weight 1, which then launches the Gaussian kernels only): kind
+  // PGO_LOSS_* or kLossFixed and parameter k (the weight itself for kLossFixed)
+  // per factor in device order, and the inverse of s1pos
   unsigned char* eloss = nullptr;   // [E] loss kind of each factor
   double* ek = nullptr;             // [E] its parameter k
   int* s1fac = nullptr;             // [E] factor at each position of the side-1 lists
@@ -98,6 +105,13 @@ hipError_t launch_error(const DevGraph& d, const double4* pose, double* out_scal
 hipError_t launch_error_lin(const DevGraph& d, const double4* pose, double* out2);
 // robust graphs only: out[e] = w(r) of device factor e at d.pose
 hipError_t launch_edge_weights(const DevGraph& d, double* out);
+// The GNC weights sweep (pgo_gnc.hip; robust graphs only) over the factors
+// marked in cand (a byte per device factor) at `pose`: with write != 0 the
+// weight of every marked factor goes into d.ek.  out5: max r^2, sum of the
+// weights, weights strictly between wtol and 1 - wtol, factors with r^2 > c2,
+// marked factors (the counts as doubles).  Uses the partial slices 0..4.
+hipError_t launch_gnc_weights(const DevGraph& d, const double4* pose, const unsigned char* cand, int loss,
+                              double mu, double c2, double wtol, int write, double* out5);
 hipError_t launch_retract(const DevGraph& d, const double* delta);
 hipError_t launch_pcg_init(const DevGraph& d, double lambda);
 hipError_t launch_pcg_spmv(const DevGraph& d, double lambda, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);

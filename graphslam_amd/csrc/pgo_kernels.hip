@@ -16,46 +16,9 @@
 #include <math.h>
 
 #include "pgo_device.h"
+#include "pgo_kernel_common.h"   // rot_normalize, sg_sum / block_sum / sum_partials, between_lin
 
 namespace pgo {
-
-// ------------------------------------------------------------ Pose2 helpers
-// GTSAM Rot2::normalize: rescale only when |c^2+s^2-1| > 1e-10.
-__device__ __forceinline__ void rot_normalize(double& c, double& s) {
-  const double scale = c * c + s * s;
-  if (fabs(scale - 1.0) > 1e-10) {
-    const double f = 1.0 / sqrt(scale);   // pow(scale, -0.5) up to rounding; taken only off the unit circle
-    c *= f;
-    s *= f;
-  }
-}
-
-// ------------------------------------------------------------ reductions
-template <int G>
-__device__ __forceinline__ double sg_sum(double v) {
-#pragma unroll
-  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-  return v;  // bit-identical in every lane of the sub-group
-}
-
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-  v = sg_sum<64>(v);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) lds[w] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < kThreads / 64; i++) s += lds[i];
-  __syncthreads();
-  return s;
-}
-
-// Sum of nb block partials; every block obtains the bit-identical value.
-__device__ __forceinline__ double sum_partials(const double* __restrict__ part, int nb, double* lds) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nb; i += kThreads) v += part[i];
-  return block_sum(v, lds);
-}
 
 // ------------------------------------------------------------ linearize
 // One sub-group of G lanes per vertex row; one lane per slot.  Each slot
@@ -561,7 +524,9 @@ __global__ __launch_bounds__(kThreads) void k_spmv(DevGraph d, double lam, const
 // w = rho'(r) / r at the linearisation point (IRLS).  A graph with any such
 // factor (d.eloss != null) runs the kernels below instead of k_linearize /
 // k_linearize_own / k_linearize_side1 / k_error; the formulas are theirs with
-// Omega scaled first.  Every weight is continuous and in (0, 1].
+// Omega scaled first.  Every m-estimator weight is continuous and in (0, 1]; a
+// fixed weight (kLossFixed, internal) is any value in [0, 1], independent of
+// the values.
 __device__ __forceinline__ double robust_weight(int kind, double k, double r2) {
   switch (kind) {
     case 1: {   // Huber
@@ -573,6 +538,7 @@ __device__ __forceinline__ double robust_weight(int kind, double k, double r2) {
       const double t = 1.0 / (1.0 + r2 / (k * k));
       return t * t;
     }
+    case kLossFixed: return k;   // a fixed weight (pgo_set_edge_weights, the GNC sweep): k holds it
     default: return 1.0;
   }
 }
@@ -585,34 +551,12 @@ __device__ __forceinline__ double robust_rho(int kind, double k, double r2) {
     }
     case 2: return 0.5 * (k * k) * log1p(r2 / (k * k));
     case 3: return 0.5 * r2 / (1.0 + r2 / (k * k));   // (k^2 / 2) r^2 / (k^2 + r^2)
+    case kLossFixed: return 0.5 * k * r2;             // w r^2 / 2
     default: return 0.5 * r2;
   }
 }
 
-// Residual of between factor (p1, p2, z) and the terms of J1 (J2 = I), as in
-// k_linearize.
-struct BetweenLin {
-  double e0, e1, e2, hc, hs, dt1, dt2;
-};
-
-__device__ __forceinline__ BetweenLin between_lin(const double4 p1, const double4 p2, const double4 z) {
-  BetweenLin b;
-  double hc = p1.z * p2.z + p1.w * p2.w, hs = -p1.w * p2.z + p1.z * p2.w;
-  rot_normalize(hc, hs);
-  const double dx = p2.x - p1.x, dy = p2.y - p1.y;
-  const double hx = p1.z * dx + p1.w * dy, hy = -p1.w * dx + p1.z * dy;
-  double ec = z.z * hc + z.w * hs, es = -z.w * hc + z.z * hs;
-  rot_normalize(ec, es);
-  const double tx = hx - z.x, ty = hy - z.y;
-  b.e0 = z.z * tx + z.w * ty;
-  b.e1 = -z.w * tx + z.z * ty;
-  b.e2 = atan2(es, ec);
-  b.hc = hc;
-  b.hs = hs;
-  b.dt1 = -p2.w * dx + p2.z * dy;
-  b.dt2 = -p2.z * dx - p2.w * dy;
-  return b;
-}
+// (the residual and J1 terms: between_lin, pgo_kernel_common.h)
 
 // w(r) of device factor e at the residual b; r^2 = e'Omega e with the unscaled Omega
 __device__ __forceinline__ double factor_weight(const DevGraph& d, int e, const BetweenLin& b, double o00,

@@ -363,3 +363,86 @@ class LevenbergMarquardtOptimizer:
 
 class GaussNewtonOptimizer(LevenbergMarquardtOptimizer):
     _params_cls = GaussNewtonParams
+
+
+class GncLossType:
+    """gtsam::GncLossType."""
+    GM = 0
+    TLS = 1
+
+
+class GncLMParams:
+    """``gtsam::GncLMParams``: the outer loop's knobs over LM inner solves
+    (pgo_gnc_params; defaults as pgo_gnc_default_params).  Known inliers are
+    indices into the factor graph, as in GTSAM; the candidates of
+    pgo_optimize_gnc are the between factors that are not among them."""
+
+    def __init__(self, lm_params: LevenbergMarquardtParams | None = None):
+        from .pose_graph import default_gnc_params
+        self.lm = lm_params if lm_params is not None else LevenbergMarquardtParams()
+        self._g = default_gnc_params()
+        self.known_inliers = []
+
+    def setLossType(self, v):
+        self._g.loss = int(v)
+
+    def setKnownInliers(self, idx):
+        self.known_inliers = sorted(int(i) for i in idx)
+
+    def setMuStep(self, v):
+        self._g.mu_step = float(v)
+
+    def setMaxIterations(self, v):
+        self._g.max_iterations = int(v)
+
+    def setRelativeCostTol(self, v):
+        self._g.relative_cost_tol = float(v)
+
+    def setWeightsTol(self, v):
+        self._g.weights_tol = float(v)
+
+    def setInlierCostThreshold(self, barc_sq):
+        """One threshold on r^2 = e' Omega e for every candidate (GTSAM: per
+        factor, on the factor error)."""
+        self._g.barc_sq = float(barc_sq)
+
+    @property
+    def raw(self):
+        return self._g
+
+
+class GncLMOptimizer:
+    """``GncOptimizer<GncLMParams>(graph, initial, params).optimize()`` /
+    ``.getWeights()`` on pgo_optimize_gnc.  Not GncOptimizer to the letter:
+    every inner solve starts from the previous result (GTSAM 4.1 restarts from
+    the initial values) and the inlier threshold is one number on r^2; priors
+    are never candidates.  Parity with GTSAM is unpinned."""
+
+    def __init__(self, graph: NonlinearFactorGraph, initial: Values, params: GncLMParams | None = None, device=0):
+        self.graph, self.initial = graph, initial
+        self.params = params if params is not None else GncLMParams()
+        self.device = device
+        self.stats = None
+        self._weights = np.ones(graph.nrFactors())
+        for f in graph.factors:
+            if isinstance(f, BetweenFactorPose2) and isinstance(f.noise, _Robust):
+                raise ValueError("GncLMOptimizer: the graph's factors must have Gaussian noise models")
+
+    def optimize(self) -> Values:
+        between = [i for i, f in enumerate(self.graph.factors) if isinstance(f, BetweenFactorPose2)]
+        known = set(self.params.known_inliers)
+        cand = [e for e, i in enumerate(between) if i not in known]
+        with _build(self.graph, self.initial, self.device) as pg:
+            self.stats = pg.optimize_gnc(candidates=cand, params=self.params.lm.raw, gnc=self.params.raw)
+            xyt = pg.poses()
+            w = pg.edge_weights() if between else np.zeros(0)
+        self._weights = np.ones(self.graph.nrFactors())
+        self._weights[between] = w
+        out = Values()
+        for k, p in zip(self.initial.keys(), xyt):
+            out.insert(k, Pose2(*p))
+        return out
+
+    def getWeights(self):
+        """One weight per factor of the graph (priors and known inliers: 1)."""
+        return self._weights.copy()

@@ -68,6 +68,49 @@ def default_params(**kw) -> L.PgoParams:
     return p
 
 
+def gnc_loss_code(loss):
+    if isinstance(loss, str):
+        if loss.lower() not in L.GNC_LOSSES:
+            raise ValueError(f"unknown GNC loss {loss!r}; have {sorted(L.GNC_LOSSES)}")
+        return L.GNC_LOSSES[loss.lower()]
+    return int(loss)
+
+
+def default_gnc_params(**kw) -> L.PgoGncParams:
+    p = L.PgoGncParams()
+    L.lib().pgo_gnc_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"pgo_gnc_params has no field {k!r}")
+        setattr(p, k, gnc_loss_code(v) if k == "loss" else v)
+    return p
+
+
+def debug_gnc_weight(loss, mu, barc_sq, r2):
+    """Host-only (pgo_debug_gnc_weight): the GNC weight of every r2."""
+    r2 = np.ascontiguousarray(np.atleast_1d(r2), dtype=np.float64)
+    w = np.zeros_like(r2)
+    rc = L.lib().pgo_debug_gnc_weight(gnc_loss_code(loss), float(mu), float(barc_sq), len(r2), L.dptr(r2), L.dptr(w))
+    if rc != L.PGO_OK:
+        raise ValueError(f"pgo_debug_gnc_weight: {rc}")
+    return w
+
+
+def debug_gnc_control(rmax_sq, cost, nonbinary, initial_error=0.0, params=None, **kw):
+    """Host-only (pgo_debug_gnc_control): the GNC control on recorded rows
+    (row 0 the plain solve).  Returns (mu per walked row, stop reason or -1
+    when the rows ran out, rows walked)."""
+    p = params if params is not None else default_gnc_params(**kw)
+    rmax_sq, cost, nonbinary = (np.ascontiguousarray(a, dtype=np.float64) for a in (rmax_sq, cost, nonbinary))
+    rows = len(cost)
+    mu, stop = np.full(max(rows, 1), np.nan), C.c_int(0)
+    n = L.lib().pgo_debug_gnc_control(C.byref(p), float(initial_error), rows, L.dptr(rmax_sq), L.dptr(cost),
+                                      L.dptr(nonbinary), L.dptr(mu), C.byref(stop))
+    if n < 0:
+        raise ValueError(f"pgo_debug_gnc_control: {n}")
+    return mu[:n].copy(), stop.value, n
+
+
 def trace_linearisations(trace, gn=False):
     """A trace's tries (solved, candidate error, model decrease) split where
     the optimiser linearised again: after every accepted try (a linearisation
@@ -208,6 +251,88 @@ class PoseGraph:
         out = np.zeros(int(n))
         self._check(self._L.pgo_get_edge_weights(self._h, int(first), int(n), L.dptr(out)))
         return out
+
+    def set_edge_weights(self, w, first=0):
+        """Fixed weights in [0, 1] on the between factors [first, first + len(w))
+        in insertion order (pgo_set_edge_weights; they must be PGO_LOSS_NONE):
+        the factor's error becomes w r^2 / 2 whatever the values, 1 makes it a
+        plain Gaussian factor again, 0 takes it out of every later solve."""
+        w = np.ascontiguousarray(np.atleast_1d(w), dtype=np.float64)
+        self._check(self._L.pgo_set_edge_weights(self._h, int(first), len(w), L.dptr(w)))
+
+    def _between(self):
+        return self.num_factors - self._priors
+
+    @staticmethod
+    def _size_t_array(idx):
+        a = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        if len(a) and a.min() < 0:
+            raise ValueError("candidate indices must be non-negative")
+        a = a.astype(np.uintp)
+        return a, a.ctypes.data_as(C.POINTER(C.c_size_t))
+
+    def optimize_gnc(self, candidates=None, params: L.PgoParams | None = None, gnc: L.PgoGncParams | None = None,
+                     **kw):
+        """Graduated non-convexity (pgo_optimize_gnc) over the between factors
+        ``candidates`` (insertion indices; None: all of them).  ``params`` /
+        keywords naming pgo_params fields configure the inner optimizes,
+        ``gnc`` / keywords naming pgo_gnc_params fields (loss also by name,
+        "gm" / "tls") the outer loop; a name both structs have
+        (``max_iterations``) goes to the outer loop.  Returns the pgo_gnc_stats
+        as a dict; ``edge_weights()`` then holds the final weights unless
+        ``keep_weights=0``."""
+        gp = gnc if gnc is not None else default_gnc_params()
+        inner_kw = {}
+        for k, v in kw.items():
+            if hasattr(gp, k):
+                setattr(gp, k, gnc_loss_code(v) if k == "loss" else v)
+            else:
+                inner_kw[k] = v
+        p = params if params is not None else default_params(**inner_kw)
+        if params is not None and inner_kw:
+            raise AttributeError(f"unknown fields {sorted(inner_kw)}")
+        if candidates is None:
+            n, ip, keep = self._between(), None, None
+        else:
+            keep, ip = self._size_t_array(candidates)
+            n = len(keep)
+            if n == 0:   # (an empty list is "none", NULL would be "all")
+                keep = np.zeros(1, np.uintp)
+                ip = keep.ctypes.data_as(C.POINTER(C.c_size_t))
+        st = L.PgoGncStats()
+        rc = self._L.pgo_optimize_gnc(self._h, C.byref(p), C.byref(gp), n, ip, C.byref(st))
+        self.last_gnc_stats = st.as_dict()
+        self._check(rc)
+        return self.last_gnc_stats
+
+    def gnc_trace(self):
+        """Per inner solve of the last optimize_gnc (pgo_get_gnc_trace), row 0
+        the plain solve: (mu, cost, sum of the candidates' weights, non-binary
+        weights, largest candidate r^2 of the sweep, inner tries, inner
+        accepted steps, inner stop reason)."""
+        n = self._check(self._L.pgo_get_gnc_trace(self._h, None, 0))
+        out = np.zeros((n, 8))
+        if n:
+            self._check(self._L.pgo_get_gnc_trace(self._h, L.dptr(out), n))
+        return out
+
+    def debug_gnc_sweep(self, loss, mu, barc_sq, candidates=None, write=False):
+        """The GNC weights sweep once at the current values
+        (pgo_debug_gnc_sweep): (one weight per between factor, non-candidates
+        1; [max r^2, sum w, non-binary at 1e-4, r^2 > barc_sq, candidates])."""
+        ne = self._between()
+        w, s5 = np.ones(ne), np.zeros(5)
+        if candidates is None:
+            n, ip, keep = ne, None, None
+        else:
+            keep, ip = self._size_t_array(candidates)
+            n = len(keep)
+            if n == 0:
+                keep = np.zeros(1, np.uintp)
+                ip = keep.ctypes.data_as(C.POINTER(C.c_size_t))
+        self._check(self._L.pgo_debug_gnc_sweep(self._h, gnc_loss_code(loss), float(mu), float(barc_sq), n, ip,
+                                                1 if write else 0, L.dptr(w), L.dptr(s5)))
+        return w, s5
 
     @classmethod
     def from_dataset(cls, g, device=0, ordering=L.PGO_ORDERING_ND):

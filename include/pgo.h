@@ -252,9 +252,10 @@ int pgo_add_edges(pgo_graph *g, size_t n, const uint64_t *k1, const uint64_t *k2
    point; the model decrease is -(g'd + d'H d / 2) on that H and g, and LM's
    guard against a vanishing model decrease compares it with the linearised
    error sum of w r^2 / 2.  Marginal covariances and the diagnostics below use
-   the weighted H.  Every weight is continuous and in (0, 1]; priors take no
+   the weighted H.  Every m-estimator weight is continuous and in (0, 1] (a
+   fixed weight, pgo_set_edge_weights below, may also be 0); priors take no
    loss.  pgo_add_edge(s) is PGO_LOSS_NONE, and a graph whose factors are all
-   PGO_LOSS_NONE computes what it did before, bit for bit. */
+   PGO_LOSS_NONE at weight 1 computes what it did before, bit for bit. */
 #define PGO_LOSS_NONE 0
 #define PGO_LOSS_HUBER 1
 #define PGO_LOSS_CAUCHY 2
@@ -271,6 +272,118 @@ int pgo_add_edges_robust(pgo_graph *g, size_t n, const uint64_t *k1, const uint6
    current values (device; 1.0 for PGO_LOSS_NONE): a caller rejects the loop
    closures whose weight ends low */
 int pgo_get_edge_weights(pgo_graph *g, size_t first, size_t n, double *out);
+
+/* ---- fixed weights on between factors ---------------------------------------
+   w in [0, 1], finite; the factors [first, first + n) in insertion order must be
+   PGO_LOSS_NONE (else PGO_E_ARG; a range past the last factor -> PGO_E_ARG).
+   The factor's error becomes w r^2 / 2 and it enters H and g with Omega replaced
+   by w Omega, whatever the values; w == 1 makes it a plain Gaussian factor again.
+   pgo_get_edge_weights returns w exactly.  A values-only change: the Cholesky
+   plan, the captured graphs and the ordering stay.  This is how a caller acts
+   on a loop closure found to be wrong: weight 0 takes it out of every later
+   solve.  With weights of 0 H may be singular: pgo_marginal_covariances* and
+   Gauss-Newton then return PGO_E_INDETERMINANT as for any singular H, and
+   LM's damping copes.  A graph whose weights are all back at 1 (and without a
+   loss) takes the Gaussian kernels again and computes what a handle that never
+   had weights computes, bit for bit. */
+int pgo_set_edge_weights(pgo_graph *g, size_t first, size_t n, const double *w);
+
+/* ---- graduated non-convexity (GNC) ------------------------------------------
+   Yang, Antonante, Tzoumas, Carlone, "Graduated Non-Convexity for Robust
+   Spatial Perception", RA-L 2020; GTSAM >= 4.1 GncOptimizer.  The candidate
+   between factors (the ones that may be outliers) get weights in [0, 1] that an
+   outer loop alternates with weighted least-squares solves while the surrogate
+   of the robust cost goes from convex to the target (mu); it needs no good
+   start.  With c^2 = barc_sq and r^2 = e' Omega e of a candidate:
+
+     row 0     one inner pgo_optimize(g, inner) with all candidate weights 1;
+               prev_cost = its final error.  No candidates: stop there.
+     sweep     rmax_sq = the largest r^2 over the candidates at the result;
+               GM:  mu = max(1, 2 rmax_sq / c^2)
+               TLS: mu = c^2 / (2 rmax_sq - c^2); not positive or not finite:
+                    stop with all weights 1 (PGO_GNC_STOP_ALL_INLIERS)
+     t = 1 .. max_iterations
+       weights at the current values (one device sweep):
+               GM:  w = (mu c^2 / (r^2 + mu c^2))^2
+               TLS: lo = mu / (mu + 1) c^2, up = (mu + 1) / mu c^2;
+                    w = 1 (r^2 <= lo), 0 (r^2 >= up), else
+                    sqrt(c^2 mu (mu + 1) / r^2) - mu
+       inner pgo_optimize, warm-started from the current values
+       cost = pgo_error (the weighted error)
+       stop when  GM: |mu - 1| < 1e-3;  TLS: no candidate weight strictly
+               between weights_tol and 1 - weights_tol (both PGO_GNC_STOP_MU);
+               or |cost - prev_cost| / max(prev_cost, 1e-7) < relative_cost_tol
+               (PGO_GNC_STOP_COST)
+       else    GM: mu = max(1, mu / mu_step);  TLS: mu *= mu_step;
+               prev_cost = cost
+     final     a read-only sweep counts the candidates with r^2 > c^2
+               (pgo_gnc_stats.outliers)
+
+   Not GncOptimizer to the letter: every inner solve starts from the previous
+   result, as in the paper (GTSAM 4.1 restarts from the initial values), and
+   barc_sq is one number on r^2 (GTSAM: a per-factor threshold on the factor
+   error).  Unverified against GTSAM itself.
+
+   Candidates must be PGO_LOSS_NONE and a graph with any factor under an
+   m-estimator loss -> PGO_E_ARG; a communicator of more than one rank ->
+   PGO_E_ARG (one rank only); an unknown loss, barc_sq <= 0, mu_step <= 1,
+   max_iterations < 0, a negative or non-finite tolerance -> PGO_E_ARG.  Fixed
+   weights the candidates hold on entry are reset to 1; the other factors keep
+   theirs.  An inner optimize that fails ends the call with its status: the
+   values are those of the last successful inner solve and the candidates'
+   weights are 1 again.  pgo_get_trace keeps describing the last inner
+   optimize. */
+#define PGO_GNC_GM 0    /* Geman-McClure surrogate, mu decreases to 1 */
+#define PGO_GNC_TLS 1   /* truncated least squares, mu increases, weights end 0 / 1 */
+typedef struct {
+  int loss;                  /* [PGO_GNC_GM] */
+  double barc_sq;            /* c^2, the inlier threshold on r^2 = e' Omega e
+                                [11.344866730144373 = chi2inv(0.99, 3)] */
+  double mu_step;            /* [1.4] */
+  int max_iterations;        /* outer iterations [100] */
+  double relative_cost_tol;  /* [1e-5] */
+  double weights_tol;        /* TLS: a weight within this of 0 or 1 is binary [1e-4] */
+  int keep_weights;          /* 1: the candidates keep their final weights as fixed
+                                weights (pgo_set_edge_weights); 0: they are plain
+                                again [1] */
+} pgo_gnc_params;
+
+#define PGO_GNC_STOP_MU 0             /* GM: mu reached 1; TLS: every weight binary */
+#define PGO_GNC_STOP_COST 1           /* relative cost change below relative_cost_tol */
+#define PGO_GNC_STOP_MAX_ITER 2
+#define PGO_GNC_STOP_NO_CANDIDATES 3  /* the call was one pgo_optimize */
+#define PGO_GNC_STOP_ALL_INLIERS 4    /* TLS: no candidate beyond the threshold after row 0 */
+#define PGO_GNC_STOP_ERROR 5          /* an inner optimize failed */
+
+typedef struct {
+  int status;                /* PGO_OK / PGO_W_MAXITER (outer limit) / error          */
+  int stop_reason;           /* PGO_GNC_STOP_*                                        */
+  int outer_iterations;      /* weight updates, row 0 not counted                     */
+  int candidates;
+  int outliers;              /* candidates with r^2 > c^2 at the final values         */
+  long long inner_tries;     /* lambda tries, summed over all inner solves            */
+  long long linearizations;  /* ... and their linearisations                          */
+  double mu_initial, mu_final;     /* NaN when no weight update ran                   */
+  double initial_error;      /* pgo_error on entry (all candidate weights 1)          */
+  double final_cost;         /* the weighted error at the final values                */
+  double ms_total, ms_inner, ms_weights;   /* host wall: the call, the inner
+                                optimizes, the sweeps with their read-backs           */
+} pgo_gnc_stats;
+
+void pgo_gnc_default_params(pgo_gnc_params *p);
+/* idx: n insertion indices of the between factors that may be outliers (no
+   duplicates); idx NULL: every between factor; n == 0 with idx != NULL: none.
+   inner NULL: pgo_default_params; gnc NULL: pgo_gnc_default_params; stats may
+   be NULL. */
+int pgo_optimize_gnc(pgo_graph *g, const pgo_params *inner, const pgo_gnc_params *gnc,
+                     size_t n, const size_t *idx, pgo_gnc_stats *stats);
+/* One row of 8 doubles per inner solve of the last pgo_optimize_gnc, row 0
+   first: mu (NaN in row 0), cost after the inner solve, sum of the candidates'
+   weights, weights strictly between weights_tol and 1 - weights_tol, the
+   largest candidate r^2 of the row's sweep (row 0: the sweep at its result),
+   inner lambda tries, inner accepted steps, inner stop_reason (PGO_STOP_*).
+   Returns the row count (rows beyond cap are not written). */
+int pgo_get_gnc_trace(const pgo_graph *g, double *out, int cap);
 
 /* ---- optimisation (graph.cpp:119, write-back :122-130) ------------------- */
 /* Runs the optimiser from the handle's current values and replaces them with
@@ -576,6 +689,31 @@ int pgo_debug_init_system(pgo_graph *g, int stage, double *hdiag, double *hoff, 
 int pgo_debug_lm_replay(const pgo_params *params, double initial_error, int ranks, int lanes,
                         int adapt_mode, int n_lin, const int *lin_ptr, const double *tries,
                         const double *lin_err, double *trace, int trace_cap, double *out, int out_cap);
+/* Host-only, no handle: the GNC outer loop's control (the initial mu, the mu
+ * schedule, the stop rules) driven as pgo_optimize_gnc drives it, on recorded
+ * rows instead of a device.  Row 0 is the plain inner solve: cost[0] its final
+ * error, rmax_sq[0] the sweep at its result; row r >= 1: cost[r] after the
+ * inner solve of outer iteration r, nonbinary[r] the non-binary weights of its
+ * sweep (rmax_sq[r] is recorded only).  mu_out[r]: the mu of row r (NaN in row
+ * 0).  Returns the rows the control walked (1 when it stops after row 0);
+ * *stop_out the PGO_GNC_STOP_* reason, -1 when the control asked for a row past
+ * the recorded ones.  initial_error is reported by the driver and read by no
+ * rule.  Bad params -> PGO_E_ARG. */
+int pgo_debug_gnc_control(const pgo_gnc_params *params, double initial_error, int rows,
+                          const double *rmax_sq, const double *cost, const double *nonbinary,
+                          double *mu_out, int *stop_out);
+/* Host-only, no handle: w[i] = the GNC weight of r2[i] under `loss` at mu and
+ * barc_sq -- the inline the sweep kernel runs. */
+int pgo_debug_gnc_weight(int loss, double mu, double barc_sq, size_t n, const double *r2, double *w);
+/* Device: the GNC weights sweep once at the current values over the n
+ * candidates idx (NULL: every between factor), as pgo_optimize_gnc runs it.
+ * w_all (may be NULL): one weight per between factor in insertion order,
+ * non-candidates reading as 1.  stats5: max r^2, sum of the weights, weights
+ * strictly between 1e-4 and 1 - 1e-4, candidates with r^2 > barc_sq,
+ * candidates.  write != 0: the candidates hold their weights afterwards as
+ * fixed weights (pgo_set_edge_weights); write == 0: the graph is as it was. */
+int pgo_debug_gnc_sweep(pgo_graph *g, int loss, double mu, double barc_sq, size_t n, const size_t *idx,
+                        int write, double *w_all, double *stats5);
 /* Host-only: the subtree partition the PGO_MULTI_PARTITION factorisation
  * uses over `size` ranks: owner[s] per supernode (rank, -1 = top front;
  * returns the supernode count, arrays filled up to cap) and out[0..size+1] =

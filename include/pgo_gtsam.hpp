@@ -220,6 +220,78 @@ class LevenbergMarquardtOptimizer {
   bool loaded_ = false;
 };
 
+// gtsam::GncParams<LevenbergMarquardtParams> / GncOptimizer (GTSAM >= 4.1) on
+// pgo_optimize_gnc.  Known inliers are indices into graph.betweens(); the other
+// between factors are the candidates, priors never are.  Not GncOptimizer to
+// the letter: every inner solve starts from the previous result (GTSAM 4.1
+// restarts from the initial values) and the inlier threshold is one number on
+// r^2 = e' Omega e (GTSAM: per factor, on the factor error).  Factors must have
+// Gaussian noise models (a robust one: std::runtime_error, the library's PGO_E_ARG).
+enum class GncLossType { GM = PGO_GNC_GM, TLS = PGO_GNC_TLS };
+
+struct GncLMParams {
+  LevenbergMarquardtParams lm;
+  pgo_gnc_params g;
+  std::vector<size_t> knownInliers;
+  GncLMParams() { pgo_gnc_default_params(&g); }
+  explicit GncLMParams(const LevenbergMarquardtParams& base) : lm(base) { pgo_gnc_default_params(&g); }
+  void setLossType(GncLossType t) { g.loss = static_cast<int>(t); }
+  void setKnownInliers(const std::vector<size_t>& idx) { knownInliers = idx; }
+  void setMuStep(double v) { g.mu_step = v; }
+  void setMaxIterations(int v) { g.max_iterations = v; }
+  void setRelativeCostTol(double v) { g.relative_cost_tol = v; }
+  void setWeightsTol(double v) { g.weights_tol = v; }
+  void setInlierCostThreshold(double barc_sq) { g.barc_sq = barc_sq; }
+};
+
+class GncLMOptimizer {
+ public:
+  GncLMOptimizer(const NonlinearFactorGraph& graph, const Values& initial, const GncLMParams& params = GncLMParams(),
+                 int device = 0)
+      : graph_(graph), initial_(initial), params_(params), device_(device) {}
+
+  Values optimize() {
+    pgo_opts o{};
+    o.device = device_;
+    struct Handle {
+      pgo_graph* g;
+      ~Handle() { pgo_destroy(g); }
+    } h{pgo_create(&o)};
+    if (!h.g) throw std::runtime_error("pgo_create failed");
+    load_graph(h.g, graph_, initial_);
+    const size_t ne = graph_.betweens().size();
+    std::vector<char> known(ne, 0);
+    for (size_t i : params_.knownInliers)
+      if (i < ne) known[i] = 1;
+    std::vector<size_t> cand;
+    for (size_t e = 0; e < ne; e++)
+      if (!known[e]) cand.push_back(e);
+    const size_t none = 0;   // (a non-null pointer with n == 0 means "no candidates")
+    const int rc = pgo_optimize_gnc(h.g, &params_.lm.p, &params_.g, cand.size(), cand.empty() ? &none : cand.data(),
+                                    &stats_);
+    if (rc < 0) throw_status(rc, h.g);
+    weights_.assign(ne, 1.0);
+    if (ne) throw_status(pgo_get_edge_weights(h.g, 0, ne, weights_.data()), h.g);
+    std::vector<double> xyt(3 * initial_.size());
+    throw_status(pgo_get_poses(h.g, initial_.size(), nullptr, xyt.data()), h.g);
+    Values out;
+    for (size_t i = 0; i < initial_.size(); i++)
+      out.insert(initial_.keys()[i], Pose2(xyt[3 * i], xyt[3 * i + 1], xyt[3 * i + 2]));
+    return out;
+  }
+  // one weight per between factor, graph.betweens() order (known inliers: 1)
+  const std::vector<double>& getWeights() const { return weights_; }
+  const pgo_gnc_stats& stats() const { return stats_; }
+
+ private:
+  const NonlinearFactorGraph& graph_;
+  const Values& initial_;
+  GncLMParams params_;
+  int device_;
+  pgo_gnc_stats stats_{};
+  std::vector<double> weights_;
+};
+
 // gtsam::lago::initialize(graph, values): linear initial values for LM, two
 // linear solves on the device (pgo_initialize_linear): the orientations, then
 // the positions with the orientations held.  `values` only names the keys, as
