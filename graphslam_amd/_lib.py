@@ -56,6 +56,7 @@ PGO_GNC_STOP_NO_CANDIDATES = 3
 PGO_GNC_STOP_ALL_INLIERS = 4
 PGO_GNC_STOP_ERROR = 5
 GNC_STOP_REASONS = {0: "mu", 1: "cost", 2: "max_iterations", 3: "no_candidates", 4: "all_inliers", 5: "error"}
+PGO_MAP_ACCUMULATE = 1
 TRANSPORTS = {0: "none", 1: "rccl", 2: "host"}
 ABI_VERSION = 6
 STOP_REASONS = {0: "converged", 1: "lambda_upper_bound", 2: "max_iterations", 3: "max_outer", 4: "small_cost_change",
@@ -142,6 +143,23 @@ class PgoGicpResult(C.Structure):
     _fields_ = [("T", C.c_double * 16), ("converged", C.c_int), ("iterations", C.c_int),
                 ("fitness", C.c_double), ("delta", C.c_double * 3), ("cov", C.c_double * 9),
                 ("keyframe", C.c_int), ("inner_iterations", C.c_int)]
+
+
+class PgoMapParams(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double),
+                ("width", C.c_int), ("height", C.c_int), ("l_occ", C.c_double), ("l_free", C.c_double),
+                ("l_min", C.c_double), ("l_max", C.c_double), ("clear_no_return", C.c_int)]
+
+
+class PgoMapStats(C.Structure):
+    _fields_ = [("status", C.c_int), ("scans", C.c_longlong), ("scans_skipped", C.c_longlong),
+                ("beams", C.c_longlong), ("beams_return", C.c_longlong), ("beams_no_return", C.c_longlong),
+                ("beams_skipped", C.c_longlong), ("updates", C.c_longlong), ("known_cells", C.c_longlong),
+                ("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_render", C.c_double),
+                ("ms_finalize", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 
@@ -248,6 +266,20 @@ def lib():
                                            C.POINTER(C.c_float), C.POINTER(C.c_int), dp,
                                            C.POINTER(PgoGicpParams), C.POINTER(PgoGicpResult)]),
         "pgo_gicp_debug_ms": (C.c_int, [vp, dp]),
+        "pgo_map_default_params": (None, [C.POINTER(PgoMapParams)]),
+        "pgo_map_create": (vp, [C.c_int, C.POINTER(PgoMapParams)]),
+        "pgo_map_destroy": (None, [vp]),
+        "pgo_map_last_error": (C.c_char_p, [vp]),
+        "pgo_map_add_scan": (C.c_int, [vp, C.c_uint64, C.c_int, C.POINTER(C.c_float), C.c_double, C.c_double,
+                                       C.c_double, C.c_double]),
+        "pgo_map_num_scans": (C.c_size_t, [vp]),
+        "pgo_map_render": (C.c_int, [vp, C.c_size_t, C.c_size_t, dp, C.c_int, C.POINTER(PgoMapStats)]),
+        "pgo_map_render_graph": (C.c_int, [vp, vp, C.c_int, C.POINTER(PgoMapStats)]),
+        "pgo_map_get_counts": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "pgo_map_get_occupancy": (C.c_int, [vp, C.POINTER(C.c_int8)]),
+        "pgo_map_debug_ms": (C.c_int, [vp, dp]),
+        "pgo_debug_map_line": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+        "pgo_debug_map_window": (C.c_int, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

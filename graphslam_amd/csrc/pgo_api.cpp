@@ -30,6 +30,7 @@
 #include "pgo_gnc.h"
 #include "pgo_init.h"
 #include "pgo_lm.h"
+#include "pgo_map.h"
 #include "pgo_structure.h"
 
 using pgo::DevGraph;
@@ -2968,3 +2969,25 @@ int pgo_debug_solve(pgo_graph* g, double lambda, const pgo_params* params, doubl
 }
 
 }  // extern "C"
+
+// ---- pgo_map_render_graph's view of a graph (pgo_map.h): the key -> index map
+// and the device pose table; the pgo_graph calls are synchronous, so the table
+// is at rest when the map's stream reads it
+namespace pgo {
+
+long long graph_vertex_index(const pgo_graph* g, uint64_t key) {
+  const auto it = g->index.find(key);
+  return it == g->index.end() ? -1 : (long long)it->second;
+}
+
+int graph_device_ordinal(const pgo_graph* g) { return g->device; }
+
+int graph_device_poses(pgo_graph* g, const void** pose, size_t* n) {
+  RC_TRY(ensure_device(g));
+  HIP_TRY(g, hipStreamSynchronize(g->d.stream));
+  *pose = g->d.pose;
+  *n = (size_t)g->d.n;
+  return PGO_OK;
+}
+
+}  // namespace pgo

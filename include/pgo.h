@@ -557,6 +557,113 @@ int pgo_gicp_align_batch(pgo_gicp *h, int B, const float *src, const int *src_n,
 /* device time (ms) of the last batch (covariance + registration kernels) */
 int pgo_gicp_debug_ms(const pgo_gicp *h, double *ms);
 
+/* ---- occupancy-grid map from keyframe scans --------------------------------
+   The reference keeps every keyframe's sensor_msgs/LaserScan next to its
+   optimised pose (Keyframe.msg: scan, pose_opti), publishes them on
+   /graph/keyframes and leaves the overlay to rviz; its simulated world
+   (willow.pgm) is an occupancy image.  A pgo_map handle stores laser scans keyed
+   like vertices and ray-casts them into an occupancy grid at given poses, on
+   the GPU: one workgroup per scan, lanes over beams.  Its own device ordinal
+   and stream, grow-only device buffers, no device touched before the first
+   render or read (like pgo_gicp).
+
+   Grid.  width x height cells of `resolution` metres, row-major, data[row *
+   width + col]; cell (col, row) covers [origin_x + col res, origin_x + (col +
+   1) res) x [origin_y + row res, origin_y + (row + 1) res): the
+   nav_msgs/OccupancyGrid layout with an identity origin orientation.  Two int32
+   planes, hit and miss.
+   World -> cell.  col = floor((wx - origin_x) / resolution), row likewise, in
+   fp64.  A scan whose pose is not finite, or whose sensor cell has |col| or
+   |row| >= 2^30, is skipped whole (pgo_map_stats.scans_skipped).
+   Beam i of a scan at pose (x, y, theta) -- the scan frame is the keyframe
+   pose, the reference has no laser offset: r = (double)ranges[i], a = theta +
+   (angle_min + i angle_increment).  NaN or r < range_min: skipped.  r >=
+   range_max (+inf included): a no-return; with clear_no_return it is traced to
+   d = range_max and every cell on it, the last included, gets miss += 1;
+   without, it is skipped.  Otherwise d = r: every cell of the line but the last
+   gets miss += 1, the last hit += 1.  End point (x + d cos a, y + d sin a).
+   Line.  The classic all-octant integer Bresenham from the sensor's cell to the
+   end point's cell, max(dx, dy) + 1 cells:
+     dx = |x1 - x0|, dy = |y1 - y0|, sx = x1 > x0 ? 1 : -1, sy = y1 > y0 ? 1 : -1,
+     err = dx - dy;  loop: visit (x, y); stop at (x1, y1); e2 = 2 err;
+     if (e2 > -dy) { err -= dy; x += sx; }  if (e2 < dx) { err += dx; y += sy; }
+   A visited cell outside the grid is skipped on its own and the walk goes on.
+   Sensor cell == end cell: only the hit (or the one miss) is counted.
+   Occupancy.  n = hit + miss; n == 0: -1 (unknown); else L = clamp(l_occ hit +
+   l_free miss, l_min, l_max), p = 1 - 1 / (1 + exp(L)), value rint(100 p) in
+   0 .. 100.  The log odds are clamped ONCE, at the end, not after every beam:
+   this is deliberate, it makes the map independent of the order of scans and
+   beams (a per-update clamp, as in the usual recursive filter, does not
+   commute).
+   Reproducibility.  The counts are integer sums (integer atomics only, no
+   floating-point atomics anywhere): the same inputs give the same planes bit
+   for bit in any scan insertion order and any launch shape.  A cell's count
+   wraps past 2^31 - 1 updates (PGO_MAP_ACCUMULATE renders add up).
+
+   Errors, all host-side before any device work.  PGO_E_ARG: resolution or an
+   origin coordinate not finite, resolution <= 0; width or height < 1, width *
+   height > 2^28; a non-finite l_*, l_min > l_max; a scan with n outside 1 ..
+   4096, range_min < 0, range_max <= range_min, range_max / resolution > 32768
+   (this bounds every beam's loop), a non-finite angle (the last beam's
+   included), more than 2^31 - 1 beams in all; a scan range past the stored
+   scans.  PGO_E_DUP_KEY: a scan key already stored.  PGO_E_NONFINITE: a
+   non-finite host pose.  PGO_E_NO_DEVICE: only at a render or a read. */
+typedef struct pgo_map pgo_map;
+typedef struct {
+  double resolution;     /* metres per cell [0.05] */
+  double origin_x, origin_y;   /* world position of the corner of cell (0, 0) [0, 0] */
+  int width, height;     /* cells [0: must be set] */
+  double l_occ, l_free;  /* log odds of one hit / one miss [0.85, -0.4] */
+  double l_min, l_max;   /* the final clamp [-2, 3.5] */
+  int clear_no_return;   /* trace the beams without a return as free space [1] */
+} pgo_map_params;
+typedef struct {
+  int status;
+  long long scans, scans_skipped;   /* scans of the call; of them skipped whole */
+  long long beams;                  /* beams of the scans not skipped = the next three */
+  long long beams_return, beams_no_return, beams_skipped;   /* no_return counts them
+                                       whether clear_no_return traces them or not */
+  long long updates;                /* sum of hit + miss over the grid after the call */
+  long long known_cells;            /* cells with hit + miss > 0 after the call */
+  double ms_total;                  /* host wall time of the call */
+  double ms_upload;                 /* host wall: staging and copies of new scans and poses */
+  double ms_render;                 /* device events: the render kernel (with the pose gather) */
+  double ms_finalize;               /* device events: counts -> occupancy and the reductions */
+} pgo_map_stats;
+void pgo_map_default_params(pgo_map_params *p);
+pgo_map *pgo_map_create(int device, const pgo_map_params *p);   /* no device touched yet; NULL on bad params */
+void pgo_map_destroy(pgo_map *m);
+const char *pgo_map_last_error(const pgo_map *m);
+/* the scan is copied; keys are the graph's vertex keys */
+int pgo_map_add_scan(pgo_map *m, uint64_t key, int n, const float *ranges, double angle_min,
+                     double angle_increment, double range_min, double range_max);
+size_t pgo_map_num_scans(const pgo_map *m);
+#define PGO_MAP_ACCUMULATE 1   /* do not clear the planes first */
+/* poses from the host: scans [first, first + n) in insertion order, xyt 3 per scan;
+   stats may be NULL */
+int pgo_map_render(pgo_map *m, size_t first, size_t n, const double *xyt, int flags, pgo_map_stats *st);
+/* every scan at the pose of its key among g's current device values, gathered on
+   the device without a round trip over PCIe (g on another device -> PGO_E_ARG; a
+   scan key that is no vertex -> PGO_E_NO_KEY before any device work) */
+int pgo_map_render_graph(pgo_map *m, pgo_graph *g, int flags, pgo_map_stats *st);
+/* the planes after the last render (zero before the first), width * height each;
+   either may be NULL */
+int pgo_map_get_counts(pgo_map *m, int32_t *hit, int32_t *miss);
+/* width * height values: -1 unknown, 0 .. 100 */
+int pgo_map_get_occupancy(pgo_map *m, int8_t *out);
+/* Diagnostics only (the map benchmark script reads it; pgo_map_stats has no
+   field for it): device time (ms) of the last render's clear pass, 0 under
+   PGO_MAP_ACCUMULATE */
+int pgo_map_debug_ms(const pgo_map *m, double *ms_clear);
+/* Host-only, no handle: the line inline the render kernel runs, from (x0, y0) to
+   (x1, y1): xy[2 k], xy[2 k + 1] = the k-th cell, up to cap cells.  Returns the
+   cell count. */
+int pgo_debug_map_line(int x0, int y0, int x1, int y1, int *xy, int cap);
+/* Host-only: side, in cells, of the square near-field window of the miss plane
+   the render kernel accumulates in LDS around the sensor cell (cells sx - side /
+   2 .. sx + side / 2 - 1, likewise in y) */
+int pgo_debug_map_window(void);
+
 /* ---- multi-GPU: speculative lambda search ---------------------
    One process per GPU, every rank holding the same graph and values.  Where
    GTSAM's LM (graph.cpp:119) tries lambda, lambda*f, lambda*f^2, ... one after
